@@ -11,10 +11,21 @@ Data: a pool of 8 distinct [8192, 1000] fp32 batches per GPU (262 MB, larger tha
 
 Usage::
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver launches N > 1 this way)
 
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the
+outputs (``--dump-outputs``) and print the line.  ``--full`` adds everything else: the
+reference's eager op chain on the same GPU (``reference_eager_same_gpu_updates_per_s``) and,
+at N > 1, the secondary sync timings (``sync_ms``); without it both fields are null.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the timed sequence returned
+and left behind in its last step as ``DIR/<name>.npy``: ``accuracy`` (float32, the value of
+the closing ``compute()`` / ``sync_and_compute()``) and this rank's ``num_correct`` /
+``num_total`` states (float64).  The data pool is seeded, so the same arguments give the same
+inputs, and two builds can be compared output for output.
 
 Timing: barrier + device synchronize, then ``t0``; K updates and the ``sync_and_compute``
 (at N > 1 an RCCL all-gather of the metric's state buffer: no rank can leave it before every
@@ -23,9 +34,9 @@ the elapsed time, max-reduced over ranks.
 
 Rehearsal switches (not used by the driver): ``BENCH_BACKEND=gloo`` runs the multi-rank path
 over gloo, ``BENCH_DEVICE=cpu`` on CPU tensors (so the exact ``torchrun --nproc-per-node 8``
-launch can be exercised without GPUs, tests/test_bench_rehearsal.py), ``BENCH_EXTRAS=0`` skips
-the secondary sync timings, ``BENCH_EXTRAS=sync`` runs only the sync diagnostics (the headline's
-own closing sync, its path, the direct-RCCL arm).
+launch can be exercised without GPUs, tests/test_bench_rehearsal.py); under ``--full``,
+``BENCH_EXTRAS=0`` skips the secondary sync timings and ``BENCH_EXTRAS=sync`` runs only the sync
+diagnostics (the headline's own closing sync, its path, the direct-RCCL arm).
 """
 
 import argparse
@@ -42,6 +53,7 @@ BATCH = 8192
 NUM_CLASSES = 1000
 POOL = 8
 BASELINE_UPDATES_PER_S = 351.0  # reference MulticlassAccuracy.update bs=8192, C=1000
+CLOCK_RAMP_S = 0.1  # a plain run's stand-in for the ~0.07 s of GPU work the --full context run does
 
 
 def _reference_eager_rate(x_pool, y_pool, iters: int) -> float:
@@ -178,12 +190,29 @@ def _sync_extras(dev: torch.device, world: int, barrier, headline_metric) -> dic
     return out
 
 
+def _dump_outputs(out_dir: str, acc: torch.Tensor, metric) -> None:
+    """What the timed sequence returned (``accuracy``) and the metric states its last update
+    left (this rank's ``num_correct`` / ``num_total``), one ``.npy`` each: a few bytes in all."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "accuracy.npy"), torch.as_tensor(acc).detach().cpu().to(torch.float32).numpy())
+    for name in ("num_correct", "num_total"):
+        state = getattr(metric, name).detach().cpu().to(torch.float64).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), state)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--warmup", type=int, default=1000)
-    ap.add_argument("--no-reference", action="store_true", help="skip the eager-ATen context run")
+    ap.add_argument("--no-reference", action="store_true", help="with --full: skip the eager-ATen context run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the eager-ATen context run and, "
+                    "at N > 1, the secondary sync timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -232,13 +261,21 @@ def main() -> None:
             else:
                 dist.barrier()
 
-    # Context measurement first (untimed for the headline): the reference's eager op chain on
-    # this GPU.  Running it before the warmup also brings the GPU out of its idle clock state,
-    # so the K timed steps see the same clocks as a long run does.
+    # Context measurement first (--full only, untimed for the headline): the reference's eager
+    # op chain on this GPU.  Running it before the warmup also brings the GPU out of its idle
+    # clock state, so the K timed steps see the same clocks as a long run does.  A run without
+    # it gets there with CLOCK_RAMP_S of the metric's own updates.
     ref_rate = None
-    if not args.no_reference and not on_cpu:
+    if args.full and not args.no_reference and not on_cpu:
         rate = _reference_eager_rate(x_pool, y_pool, 2000)
         ref_rate = rate if rank == 0 else None
+    elif not on_cpu:
+        ramp_end = time.perf_counter() + CLOCK_RAMP_S
+        while time.perf_counter() < ramp_end:
+            for i in range(256):
+                metric.update(x_pool[i % POOL], y_pool[i % POOL])
+            device_sync()
+        metric.reset()
 
     # No automatic Python garbage-collection pass inside the warmup + ~140 us region (as timeit
     # does), and no explicit collect either: any idle gap between the warmup and t0 lets the GPU
@@ -304,11 +341,14 @@ def main() -> None:
             "sync_ms": None,
         }
 
-    # Secondary sync timings (N > 1) run AFTER the headline is final.  A collective that one
-    # rank abandons (an exception inside an extra) would leave the others blocked forever, so a
+    if args.dump_outputs is not None and rank == 0:
+        _dump_outputs(args.dump_outputs, acc, metric)
+
+    # Secondary sync timings (--full, N > 1) run AFTER the headline is final.  A collective that
+    # one rank abandons (an exception inside an extra) would leave the others blocked forever, so a
     # watchdog bounds the whole section: on expiry rank 0 prints the headline line without the
     # extras and every rank exits 0 - the driver always gets its one JSON line.
-    if world > 1 and os.environ.get("BENCH_EXTRAS", "1") != "0":
+    if args.full and world > 1 and os.environ.get("BENCH_EXTRAS", "1") != "0":
         import threading
 
         def _bail():

@@ -1,4 +1,7 @@
-"""Generate ``golden.pt``: the reference's outputs on every case in ``cases.py``.
+"""Generate ``golden.pt``: the reference's outputs on every case in ``cases.py``; and, under
+``tests/golden/``, ``cpu_fast_paths.pt`` (the reference's side of ``tests/test_cpu_fast_paths.py``,
+from ``cpu_fast_cases.py``) and ``reference_signatures.json`` (its public signatures, from
+``signature_records.py``).
 
 Run from the repo root with the reference mounted (CPU only, a few seconds)::
 
@@ -19,6 +22,10 @@ sys.path.insert(0, HERE)
 
 import _refload  # noqa: E402
 import cases  # noqa: E402
+import cpu_fast_cases  # noqa: E402
+import signature_records  # noqa: E402
+
+GOLDEN_DIR = os.path.join(os.path.dirname(HERE), "golden")
 
 
 def plain(obj):
@@ -28,6 +35,8 @@ def plain(obj):
         return tuple(plain(o) for o in obj)
     if isinstance(obj, list):
         return [plain(o) for o in obj]
+    if isinstance(obj, dict):
+        return {k: plain(v) for k, v in obj.items()}
     if isinstance(obj, (int, float, bool, str)) or obj is None:
         return obj
     raise TypeError(f"unsupported output type {type(obj)}")
@@ -95,6 +104,14 @@ def main() -> None:
     for cid, v in out["errors"].items():
         if not isinstance(v, dict):
             print("  reference does not raise:", cid)
+    os.makedirs(GOLDEN_DIR, exist_ok=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        fast = plain(cpu_fast_cases.reference_records(M, F))
+    torch.save(fast, os.path.join(GOLDEN_DIR, "cpu_fast_paths.pt"))
+    entries = signature_records.record(M, F)
+    signature_records.write(entries)
+    print(f"wrote {GOLDEN_DIR}: {len(fast)} cpu fast-path cases, {len(entries)} signatures")
 
 
 if __name__ == "__main__":

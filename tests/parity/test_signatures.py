@@ -4,19 +4,17 @@ For each name in the reference's ``metrics.__all__`` / ``metrics.functional.__al
 ``__init__`` and the ``update`` / ``compute`` / ``merge_state`` they define) and the public
 functions / classes of ``metrics.toolkit``, ``metrics.synclib``, ``tools`` and
 ``utils.random_data``, every reference parameter must exist here with the same kind, default
-and position.  Parameters the reference lacks are allowed only through ``ALLOWED_EXTRA`` (each
-one a deliberate, documented addition); a changed default only through ``ALLOWED_DEFAULT``.
+and position.  The reference's side is recorded in tests/golden/reference_signatures.json
+(tests/parity/signature_records.py; gen_goldens.py writes it).  Parameters the reference lacks
+are allowed only through ``ALLOWED_EXTRA`` (each one a deliberate, documented addition); a
+changed default only through ``ALLOWED_DEFAULT``.
 Private plumbing (an ``_err=`` argument and the like) therefore fails this test.
 """
 
 import importlib
 import inspect
 
-import pytest
-
-from tests.parity import _refload
-
-pytestmark = pytest.mark.skipif(not _refload.available(), reason="reference not mounted")
+from tests.parity import signature_records
 
 # (qualified name, parameter): additions that are part of this package's documented API
 ALLOWED_EXTRA = {
@@ -36,11 +34,12 @@ ALLOWED_DEFAULT = {
     # the reference's constructor default k=1 with its hard-coded topk(k=2) crash
     ("TopKMultilabelAccuracy.__init__", "k"),
 }
-EXTRA_MODULES = ("metrics.toolkit", "metrics.synclib", "tools", "tools.flops", "tools.module_summary",
-                 "utils.random_data")
 
 
 def _params(f):
+    """Parameters by name: of a callable of ours, or as recorded for the reference's."""
+    if f is None or isinstance(f, dict):
+        return f
     try:
         return inspect.signature(f).parameters
     except (TypeError, ValueError):
@@ -80,35 +79,14 @@ def _diff(tag, ours, ref):
 
 
 def _pairs():
-    RM, RF = _refload.load()
-    import torcheval_amd.metrics as M
-    import torcheval_amd.metrics.functional as F
-
-    for mod, ref in ((F, RF), (M, RM)):
-        for name in ref.__all__:
-            r, o = getattr(ref, name), getattr(mod, name)
-            if inspect.isclass(r):
-                yield f"{name}.__init__", o.__init__, r.__init__
-                for meth in ("update", "compute", "merge_state"):
-                    if meth in r.__dict__:
-                        yield f"{name}.{meth}", getattr(o, meth), getattr(r, meth)
-            elif callable(r):
-                yield name, o, r
-    for modname in EXTRA_MODULES:
-        r = importlib.import_module("torcheval." + modname)
-        o = importlib.import_module("torcheval_amd." + modname)
-        names = getattr(r, "__all__", None) or [
-            n for n, v in vars(r).items()
-            if not n.startswith("_") and (inspect.isfunction(v) or inspect.isclass(v))
-            and getattr(v, "__module__", "") == r.__name__
-        ]
-        for name in names:
-            rv, ov = getattr(r, name), getattr(o, name, None)
-            assert ov is not None, f"torcheval_amd.{modname}.{name} is absent"
-            if inspect.isclass(rv):
-                yield f"{modname}.{name}.__init__", ov.__init__, rv.__init__
-            elif callable(rv):
-                yield f"{modname}.{name}", ov, rv
+    """(tag, our callable, the reference's recorded parameters) for every recorded callable."""
+    for e in signature_records.load():
+        mod = importlib.import_module("torcheval_amd." + e["module"])
+        ours = getattr(mod, e["name"], None)
+        assert ours is not None, f"torcheval_amd.{e['module']}.{e['name']} is absent"
+        if e["member"] is not None:
+            ours = getattr(ours, e["member"])
+        yield e["tag"], ours, e["params"]
 
 
 def test_every_public_signature_matches_the_reference():

@@ -1,6 +1,7 @@
 """The driver's exact N=8 launch of bench.py (torch.distributed.run, 8 processes, 127.0.0.1)
 rehearsed on CPU tensors over gloo: every rank runs the multi-rank timed region (updates +
-sync_and_compute through the state-buffer engine) and rank 0 prints the one JSON line."""
+sync_and_compute through the state-buffer engine) and rank 0 prints the one JSON line, with the
+``--full`` sync diagnostics."""
 
 import json
 import os
@@ -21,7 +22,7 @@ def test_bench_8_rank_launch_on_cpu():
     env = dict(os.environ, BENCH_DEVICE="cpu", BENCH_EXTRAS="sync", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py",
-           "--gpus", "8", "--steps", "3", "--warmup", "1"]
+           "--gpus", "8", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,8 +1,9 @@
 """The small-batch CPU host calls (csrc/runtime/cpu_metrics.cpp: cpu_class_metric,
 cpu_class_average, cpu_confusion, cpu_moments_update) and the no-context append / compute
-paths, differential against the reference itself (loaded read-only from /root/reference) on
-random batches with missing classes, NaN scores, ties, int32 targets and both input forms.
-Skips when the reference is not mounted."""
+paths, differential against the reference itself on random batches with missing classes, NaN
+scores, ties, int32 targets and both input forms.  The reference's side of every comparison is
+recorded in tests/golden/cpu_fast_paths.pt (tests/parity/gen_goldens.py writes it from
+tests/parity/cpu_fast_cases.py, which also builds the inputs used here)."""
 
 import logging
 import os
@@ -13,29 +14,22 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "parity"))
 
-import _refload  # noqa: E402
+import cpu_fast_cases as cases  # noqa: E402
 
 from torcheval_amd import metrics as M  # noqa: E402
 from torcheval_amd.metrics import functional as F  # noqa: E402
 from torcheval_amd.ops import native_loaded  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not _refload.available() or not native_loaded(),
-                                reason="reference or native build absent")
+pytestmark = pytest.mark.skipif(not native_loaded(), reason="native build absent")
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpu_fast_paths.pt")
+_batches = cases.batches
 
 
 @pytest.fixture(scope="module")
 def ref():
-    return _refload.load()
-
-
-def _batches(seed: int, n: int = 8, c: int = 6):
-    g = torch.Generator().manual_seed(seed)
-    scores = torch.randn(n, c, generator=g)
-    scores[0, 1] = float("nan") if seed % 3 == 0 else scores[0, 1]
-    scores[1] = 0.25  # an all-tie row: argmax is the first index
-    target = torch.randint(0, c - 2, (n,), generator=g)  # the last two classes never appear
-    labels = torch.randint(0, c, (n,), generator=g)
-    return scores, target, labels
+    """The reference's recorded results, by case key."""
+    return torch.load(GOLDEN, weights_only=True)
 
 
 def _same(a: torch.Tensor, b: torch.Tensor) -> None:
@@ -43,35 +37,26 @@ def _same(a: torch.Tensor, b: torch.Tensor) -> None:
     torch.testing.assert_close(a, b, equal_nan=True, rtol=2e-6, atol=1e-7)
 
 
-@pytest.mark.parametrize("seed", range(6))
-@pytest.mark.parametrize("fn,averages", [
-    ("multiclass_accuracy", ("macro",)),
-    ("multiclass_f1_score", ("macro", "weighted")),
-    ("multiclass_precision", ("macro", "weighted")),
-    ("multiclass_recall", ("macro", "weighted")),
-])
+@pytest.mark.parametrize("seed", cases.MACRO_WEIGHTED_SEEDS)
+@pytest.mark.parametrize("fn,averages", cases.MACRO_WEIGHTED)
 def test_macro_weighted_functionals_match_reference(ref, seed, fn, averages, caplog):
-    RM, RF = ref
-    scores, target, labels = _batches(seed)
-    for avg in averages:
-        for inp in (scores, labels, scores.double()):
-            for tgt in (target, target.int()) if inp is scores else (target,):
-                caplog.clear()
-                with caplog.at_level(logging.WARNING):
-                    ours = getattr(F, fn)(inp, tgt, num_classes=6, average=avg)
-                ours_log = [r.getMessage() for r in caplog.records]
-                caplog.clear()
-                try:
-                    with caplog.at_level(logging.WARNING):
-                        theirs = getattr(RF, fn)(inp, tgt.long(), num_classes=6, average=avg)
-                    theirs_log = [r.getMessage() for r in caplog.records]
-                except RuntimeError:
-                    # the reference's recall divides the masked tp by the unmasked labels and
-                    # crashes once a class has neither labels nor predictions (docs/parity.md)
-                    assert fn == "multiclass_recall"
-                    theirs, theirs_log = _masked_recall(inp, tgt, avg), ours_log
-                _same(ours, theirs)
-                assert ours_log == theirs_log
+    calls = list(cases.macro_weighted_inputs(seed, averages))
+    recorded = ref[f"macro_weighted/{fn}/{seed}"]
+    assert len(recorded) == len(calls)
+    for (avg, inp, tgt), rec in zip(calls, recorded):
+        caplog.clear()
+        with caplog.at_level(logging.WARNING):
+            ours = getattr(F, fn)(inp, tgt, num_classes=6, average=avg)
+        ours_log = [r.getMessage() for r in caplog.records]
+        if "raises" in rec:
+            # the reference's recall divides the masked tp by the unmasked labels and
+            # crashes once a class has neither labels nor predictions (docs/parity.md)
+            assert fn == "multiclass_recall" and rec["raises"] == "RuntimeError"
+            theirs, theirs_log = _masked_recall(inp, tgt, avg), ours_log
+        else:
+            theirs, theirs_log = rec["value"], rec["log"]
+        _same(ours, theirs)
+        assert ours_log == theirs_log
 
 
 def _masked_recall(inp, tgt, avg):
@@ -84,16 +69,13 @@ def _masked_recall(inp, tgt, avg):
     return r.mean() if avg == "macro" else (r * (lab[mask] / lab.sum())).sum()
 
 
-@pytest.mark.parametrize("k", [2, 3])
+@pytest.mark.parametrize("k", cases.TOP_K)
 def test_macro_accuracy_top_k(ref, k):
-    _, RF = ref
     scores, target, _ = _batches(11)
-    _same(F.multiclass_accuracy(scores, target, average="macro", num_classes=6, k=k),
-          RF.multiclass_accuracy(scores, target, average="macro", num_classes=6, k=k))
+    _same(F.multiclass_accuracy(scores, target, average="macro", num_classes=6, k=k), ref[f"top_k/{k}"])
 
 
-def test_out_of_range_labels_still_raise_the_reference_errors(ref):
-    _, RF = ref
+def test_out_of_range_labels_still_raise_the_reference_errors():
     scores, target, labels = _batches(1)
     bad = target.clone()
     bad[3] = 6
@@ -108,53 +90,25 @@ def test_out_of_range_labels_still_raise_the_reference_errors(ref):
         F.multiclass_confusion_matrix(torch.zeros(0, dtype=torch.long), torch.zeros(0, dtype=torch.long), num_classes=6)
 
 
-@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("seed", cases.CONFUSION_SEEDS)
 def test_confusion_functionals_match_reference(ref, seed):
-    _, RF = ref
-    scores, target, labels = _batches(seed)
-    for inp in (scores, labels, scores.double()):
-        _same(F.multiclass_confusion_matrix(inp, target, num_classes=6),
-              RF.multiclass_confusion_matrix(inp, target, num_classes=6))
-    _same(F.multiclass_confusion_matrix(scores, target.int(), num_classes=6),
-          RF.multiclass_confusion_matrix(scores, target.int(), num_classes=6))
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(9, generator=g)
-    x[2] = float("nan")
-    x[4] = 0.5  # on the threshold: predicts 1
-    y = torch.randint(0, 2, (9,), generator=g)
-    for thr in (0.5, 0.3):
-        _same(F.binary_confusion_matrix(x, y, threshold=thr), RF.binary_confusion_matrix(x, y, threshold=thr))
-    _same(F.binary_confusion_matrix(x, y, normalize="all"), RF.binary_confusion_matrix(x, y, normalize="all"))
+    calls = list(cases.confusion_inputs(seed))
+    recorded = ref[f"confusion/{seed}"]
+    assert len(recorded) == len(calls) == 7
+    for (name, args, kwargs), theirs in zip(calls, recorded):
+        _same(getattr(F, name)(*args, **kwargs), theirs)
 
 
-@pytest.mark.parametrize("cls,kw", [
-    ("MulticlassF1Score", {"num_classes": 6, "average": "macro"}),
-    ("MulticlassF1Score", {"num_classes": 6, "average": "weighted"}),
-    ("MulticlassPrecision", {"num_classes": 6, "average": "macro"}),
-    # (recall over batches where every class occurs: the reference crashes otherwise)
-    ("MulticlassRecall", {"num_classes": 6, "average": "weighted"}),
-    ("MulticlassAccuracy", {"num_classes": 6, "average": "macro"}),
-    ("MulticlassConfusionMatrix", {"num_classes": 6}),
-    ("MulticlassConfusionMatrix", {"num_classes": 6, "normalize": "true"}),
-])
+@pytest.mark.parametrize("cls,kw", cases.CLASS_CASES)
 def test_class_computes_match_reference(ref, cls, kw):
-    RM, _ = ref
-    ours, theirs = getattr(M, cls)(**kw), getattr(RM, cls)(**kw)
-    for seed in range(3):
-        scores, target, labels = _batches(seed)
-        if cls == "MulticlassRecall":
-            target = torch.arange(8) % 6
-        ours.update(scores, target)
-        theirs.update(scores, target)
-        _same(ours.compute(), theirs.compute().to(ours.compute().dtype))
-    ours.reset()
-    theirs.reset()
-    scores, target, _ = _batches(7)
-    if cls == "MulticlassRecall":
-        target = torch.arange(8).flip(0) % 6
-    ours.update(scores, target)
-    theirs.update(scores, target)
-    _same(ours.compute(), theirs.compute().to(ours.compute().dtype))
+    ours, recorded = getattr(M, cls)(**kw), iter(ref[cases.class_key(cls, kw)])
+    first, second = cases.class_updates(cls)
+    assert len(first) == 3 and len(second) == 1 and len(ref[cases.class_key(cls, kw)]) == 4
+    for run in (first, second):
+        for scores, target in run:
+            ours.update(scores, target)
+            _same(ours.compute(), next(recorded).to(ours.compute().dtype))
+        ours.reset()
 
 
 def test_confusion_compute_is_not_aliased_into_a_state_buffer():
@@ -165,46 +119,36 @@ def test_confusion_compute_is_not_aliased_into_a_state_buffer():
     assert out.sum().item() == 3
 
 
-@pytest.mark.parametrize("shape", [(8,), (8, 4), (1, 3), (5, 1)])
+@pytest.mark.parametrize("shape", cases.REGRESSION_SHAPES)
 @pytest.mark.parametrize("weighted", [False, True])
 def test_regression_class_updates_match_reference(ref, shape, weighted):
-    RM, _ = ref
-    g = torch.Generator().manual_seed(len(shape) * 10 + shape[0])
-    ours_mse, ref_mse = M.MeanSquaredError(), RM.MeanSquaredError()
-    ours_r2, ref_r2 = M.R2Score(), RM.R2Score()
-    for _ in range(3):
-        x, t = torch.rand(shape, generator=g), torch.rand(shape, generator=g)
-        w = torch.rand(shape[0], generator=g) if weighted else None
+    rec = ref[cases.regression_key(shape, weighted)]
+    ours_mse, ours_r2 = M.MeanSquaredError(), M.R2Score()
+    for x, t, w in cases.regression_updates(shape, weighted):
         if weighted:
             ours_mse.update(x, t, sample_weight=w)
-            ref_mse.update(x, t, sample_weight=w)
         else:
             ours_mse.update(x, t)
-            ref_mse.update(x, t)
         if shape[0] >= 2:
             ours_r2.update(x, t)
-            ref_r2.update(x, t)
-    for a, b in ((ours_mse.sum_squared_error, ref_mse.sum_squared_error), (ours_mse.sum_weight, ref_mse.sum_weight)):
-        _same(a, b.to(a.dtype))
-    _same(ours_mse.compute(), ref_mse.compute())
+    for a, b in ((ours_mse.sum_squared_error, rec["sum_squared_error"]), (ours_mse.sum_weight, rec["sum_weight"])):
+        _same(a, torch.as_tensor(b).to(a.dtype))
+    _same(ours_mse.compute(), rec["mse"])
+    assert ("r2" in rec) == (shape[0] >= 2)
     if shape[0] >= 2:
-        for name in ("sum_squared_obs", "sum_obs", "sum_squared_residual", "num_obs"):
-            a, b = getattr(ours_r2, name), getattr(ref_r2, name)
-            _same(a, b.to(a.dtype))
-        _same(ours_r2.compute(), ref_r2.compute())
+        for name in cases.R2_STATES:
+            a = getattr(ours_r2, name)
+            _same(a, torch.as_tensor(rec[name]).to(a.dtype))
+        _same(ours_r2.compute(), rec["r2"])
 
 
-@pytest.mark.parametrize("cls", ["BinaryAUROC", "BinaryAUPRC"])
+@pytest.mark.parametrize("cls", cases.SAMPLE_STORE_CLASSES)
 def test_sample_store_appends_keep_the_callers_tensors(ref, cls):
-    RM, _ = ref
-    ours, theirs = getattr(M, cls)(), getattr(RM, cls)()
-    g = torch.Generator().manual_seed(3)
-    for _ in range(4):
-        x, y = torch.rand(8, generator=g), torch.randint(0, 2, (8,), generator=g)
+    ours = getattr(M, cls)()
+    for x, y in cases.sample_store_updates():
         ours.update(x, y)
-        theirs.update(x, y)
         assert ours.inputs[-1] is x and ours.targets[-1] is y  # the reference's no-op .to
-    _same(ours.compute(), theirs.compute())
+    _same(ours.compute(), ref[f"sample_store/{cls}"])
     with pytest.raises(ValueError):
         ours.update(torch.rand(3), torch.rand(4))
     state = ours.state_dict()

@@ -7,10 +7,15 @@ test of the session.  A job is a picklable callable ``fn(rank, world_size, *args
 every rank at once; results come back in rank order, and any rank's exception is re-raised
 in the parent with its traceback.  A job that does not finish in ``timeout`` seconds (e.g. a
 rank died mid-collective) kills the pool; the next job starts a new one.
+
+Results travel as pickled bytes, not as shared-memory tensors: the queue's own tensor pickling
+keeps one open file descriptor per received storage, and a job that returns a few hundred
+tensors from every rank runs into an ordinary user's limit of 1024 open files.
 """
 
 import atexit
 import os
+import pickle
 import queue
 import socket
 import traceback
@@ -44,7 +49,7 @@ def _worker(rank: int, world_size: int, port: int, jobs, results) -> None:
         job_id, fn, args = job
         try:
             out = fn(rank, world_size, *args)
-            results.put((job_id, rank, True, out))
+            results.put((job_id, rank, True, pickle.dumps(out)))
         except BaseException:  # noqa: B902 - report everything to the parent
             results.put((job_id, rank, False, traceback.format_exc()))
     dist.destroy_process_group()
@@ -88,7 +93,7 @@ class DistWorkerPool:
             if jid != job_id:
                 continue
             if ok:
-                out[rank] = payload
+                out[rank] = pickle.loads(payload)
             else:
                 errors.append((rank, payload))
         if errors:
