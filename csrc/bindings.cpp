@@ -301,6 +301,17 @@ Tensor rank_scores(const Tensor& input, const Tensor& target, int64_t mode, int6
   return out;
 }
 
+// ATen compares a tensor with a Python threshold in the tensor's dtype: the threshold is cast to
+// it (round to nearest even, c10's conversions) before ``x < threshold``.  Every bf16 / f16 score
+// is exact in float32, so a float32 compare against the rounded threshold decides identically.
+// Other dtypes: float32 (float32 scores; integer and bool scores promote to it).
+static float threshold_as(const Tensor& scores, double threshold) {
+  const float t = static_cast<float>(threshold);
+  if (scores.scalar_type() == at::kBFloat16) return static_cast<float>(c10::BFloat16(t));
+  if (scores.scalar_type() == at::kHalf) return static_cast<float>(c10::Half(t));
+  return t;
+}
+
 void binary_counts(const Tensor& input, const Tensor& target, const optional<Tensor>& weight,
                    double threshold, const optional<Tensor>& tp, const optional<Tensor>& fp,
                    const optional<Tensor>& tn, const optional<Tensor>& fn,
@@ -326,7 +337,8 @@ void binary_counts(const Tensor& input, const Tensor& target, const optional<Ten
   a.target = tg.data_ptr();
   a.tg_dt = dt_of(tg);
   a.n = in.numel();
-  a.threshold = static_cast<float>(threshold);
+  a.threshold = threshold_as(in, threshold);
+  a.threshold64 = threshold;
   a.strict_binary = static_cast<int>(strict);
   a.out[0] = f32_out(tp, input, 1, "tp");
   a.out[1] = f32_out(fp, input, 1, "fp");
@@ -1392,7 +1404,7 @@ void multilabel_counts(const Tensor& input, const Tensor& target, double thresho
   a.t_row_stride = target.stride(0);
   a.n = input.size(0);
   a.c = input.size(1);
-  a.threshold = static_cast<float>(threshold);
+  a.threshold = threshold_as(input, threshold);
   a.k = static_cast<int>(k);
   a.criteria = static_cast<int>(criteria);
   a.num_correct = num_correct.data_ptr<float>();

@@ -53,7 +53,8 @@ struct BinaryCountsArgs {
   const void* weight = nullptr;
   DType w_dt = DType::f32;
   int64_t n = 0;
-  float threshold = 0.5f;
+  float threshold = 0.5f;     // rounded to the score dtype by the caller (bf16 / f16), widened to f32
+  double threshold64 = 0.5;   // float64 scores compare in double
   int strict_binary = 0;  // non-{0,1} targets count nowhere (1) or as the "other" class (0)
   float* out[4] = {nullptr, nullptr, nullptr, nullptr};   // tp, fp, tn, fn
   float* out2[4] = {nullptr, nullptr, nullptr, nullptr};  // optional second destinations

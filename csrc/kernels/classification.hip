@@ -676,14 +676,20 @@ __global__ __launch_bounds__(kBlock) void cls_labels_kernel(ClsCountsArgs a) {
 }
 
 // Binary: thresholded scores vs targets -> [tp, fp, tn, fn] (+ optional weights).
+// The decision is ATen's torch.where(x < threshold, 0, 1) in the score dtype.  F64: float64 scores
+// against the double threshold.  Otherwise a float32 compare against a.threshold, which the host
+// has rounded to the score dtype (bf16 / f16 scores widen exactly; integer and bool scores
+// promote to float32, as an integer tensor against a Python float does).
+template <bool F64>
 __global__ __launch_bounds__(kBlock) void binary_counts_kernel(BinaryCountsArgs a) {
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
-    const float x = load_as_f32(a.input, a.in_dt, i);
     const double t = load_as_f64(a.target, a.tg_dt, i);
     const float w = a.weight ? load_as_f32(a.weight, a.w_dt, i) : 1.f;
-    const bool pos = !(x < a.threshold);
+    bool pos;
+    if constexpr (F64) pos = !(load_as_f64(a.input, DType::f64, i) < a.threshold64);
+    else pos = !(load_as_f32(a.input, a.in_dt, i) < a.threshold);
     const bool t1 = t == 1.0, t0 = t == 0.0;
     const float other = a.strict_binary ? 0.f : w;
     if (pos) {
@@ -818,7 +824,8 @@ int launch_binary_counts(const BinaryCountsArgs& a, hipStream_t stream) {
   if (a.n <= 0) return 0;
   const int cap = a.max_blocks > 0 ? a.max_blocks : 256;
   const int grid = stream_grid(a.n, kBlock * 4, cap);
-  hipLaunchKernelGGL(binary_counts_kernel, dim3(grid), dim3(kBlock), 0, stream, a);
+  if (a.in_dt == DType::f64) hipLaunchKernelGGL(binary_counts_kernel<true>, dim3(grid), dim3(kBlock), 0, stream, a);
+  else hipLaunchKernelGGL(binary_counts_kernel<false>, dim3(grid), dim3(kBlock), 0, stream, a);
   return static_cast<int>(hipGetLastError());
 }
 

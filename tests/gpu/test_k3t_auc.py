@@ -49,6 +49,42 @@ def test_matches_aten(tasks, n):
     torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5 * float(y.abs().max()))
 
 
+def _integer_y(kind, tasks, n, g):
+    if kind == "int64_small":
+        return torch.randint(-5, 6, (tasks, n), generator=g)
+    if kind == "int64_large":
+        # past what the low 32 bits of an int64 hold: a loader that truncates returns other values
+        vals = torch.tensor([2**31, -(2**31), 2**31 - 1, 2**31 + 1, -(2**31) - 1, 2**32 + 3, 2**40, -(2**40), 0, 7])
+        y = vals[torch.randint(0, vals.numel(), (tasks, n), generator=g)]
+        y[:, 0] = 2**32 + 3  # present even at n = 2
+        return y
+    if kind == "int32":
+        y = torch.randint(-(2**31) + 1, 2**31, (tasks, n), generator=g).to(torch.int32)
+        y[:, 0] = 2**31 - 1
+        y[:, -1] = -(2**31) + 1
+        return y
+    assert kind == "uint8"
+    return torch.randint(0, 256, (tasks, n), generator=g).to(torch.uint8)
+
+
+@pytest.mark.parametrize("n", [2, 1000, 4097])
+@pytest.mark.parametrize("kind", ["int64_small", "int64_large", "int32", "uint8"])
+def test_integer_y_matches_trapz_promotion(kind, n):
+    """Integer y: torch.trapz adds neighbouring y in y's own dtype (uint8 and int32 sums wrap)
+    and promotes to float32 afterwards, whatever the magnitude.  The oracle is that ATen chain
+    itself on the CPU (not the fp64 ``_ref``, which would hide both the wrapping and how large
+    integers round)."""
+    tasks = 3
+    g = torch.Generator().manual_seed(n * 13 + len(kind))
+    x = torch.rand(tasks, n, generator=g)
+    y = _integer_y(kind, tasks, n, g)
+    xs, idx = torch.sort(x, dim=1, stable=True)
+    ref = torch.trapz(y.gather(1, idx), xs)
+    assert ref.dtype == torch.float32
+    got = auc(x.to(DEV), y.to(DEV), reorder=True).cpu()
+    torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5 * float(y.float().abs().max()))
+
+
 def test_ties_keep_input_order():
     # many equal x: the y order inside a tie group decides the boundary trapezoids (stable sort)
     g = torch.Generator().manual_seed(5)

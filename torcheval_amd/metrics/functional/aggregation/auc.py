@@ -14,12 +14,15 @@ from torcheval_amd.ops import use_native
 
 __all__ = ["auc"]
 
-_Y_DTYPES = (torch.float32, torch.int64, torch.int32, torch.uint8, torch.bool)
+# Only float32 y takes the native path.  torch.trapz adds neighbouring y in y's own dtype before
+# it promotes, so integer y wraps there (uint8 200 + 200 is 144; int32 and int64 likewise) and
+# bool y raises: integer and bool y keep the ATen form below, which is that arithmetic itself.
+_Y_DTYPES = (torch.float32,)
 
 
 def _auc_native(x: torch.Tensor, y: torch.Tensor) -> Optional[torch.Tensor]:
     """float32 [tasks] areas of the x-sorted pairs, or None when the native path does not apply."""
-    # y rides K3a's target payload, converted to its f32 value (as trapz's float32 promotion does)
+    # y rides K3a's target payload as its f32 bits
     if not (use_native(x) and x.dtype == torch.float32 and y.dtype in _Y_DTYPES and y.device == x.device
             and x.shape == y.shape and x.shape[-1] < 2**31):
         return None

@@ -14,6 +14,7 @@ from typing import Optional, Tuple
 
 import torch
 
+import torcheval_amd.ops as _ops
 from torcheval_amd.ops import compiling, native, native_loaded, use_native
 from torcheval_amd.ops.classification import (
     binary_counts,
@@ -60,6 +61,7 @@ def _cpu_binary_ok(input: torch.Tensor, target: torch.Tensor) -> bool:
         and input.numel() <= _CPU_FAST_MAX
         and not input.requires_grad
         and not compiling()
+        and not _ops.DISABLE_HIP  # read at call time: the ATen chain, as for the other host twins
         and native_loaded()
     )
 

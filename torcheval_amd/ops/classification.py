@@ -82,6 +82,7 @@ def _cpu_prf_ok(input: torch.Tensor, target: torch.Tensor) -> bool:
         and input.numel() <= _CPU_PRF_MAX
         and not input.requires_grad
         and not compiling()
+        and not _ops.DISABLE_HIP
         and native_loaded()
     )
 
