@@ -222,6 +222,16 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: m.update(w, clicks, w)
         return make
 
+    def ssim(cls):
+        def make():
+            side = 256 if s >= 1 else 16
+            x, t = rand(n(64), 3, side, side), rand(n(64), 3, side, side)
+            if cls:
+                m = M.StructuralSimilarity(device=dev)
+                return lambda: m.update(x, t)
+            return lambda: F.structural_similarity(x, t)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -370,6 +380,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "Sum.update 8192x1000 (K5b)": k5b(M.Sum, "sum"),
         "Mean.update 8192x1000 (K5b)": k5b(M.Mean, "sum"),
         "PeakSignalNoiseRatio.update 8192x1000 (K5b)": k5b(M.PeakSignalNoiseRatio, "psnr"),
+        "structural_similarity 64x3x256x256 (K12)": ssim(False),
+        "StructuralSimilarity.update 64x3x256x256 (K12)": ssim(True),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),
         "WeightedCalibration(64 tasks).update 8192x1000 (K5b)": k5b(M.WeightedCalibration, "wc"),
         "WindowedClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.WindowedClickThroughRate, "ctr"),

@@ -1322,6 +1322,56 @@ void trapz_sorted(const Tensor& x, const Tensor& y_bits, const Tensor& out) {
                "trapz_sorted");
 }
 
+// K12: structural similarity (csrc/kernels/ssim.hip).  ``out`` takes the [n] per-image values, or
+// their mean when ``mean``; the optional class states take += sum of the values and += n.
+void ssim(const Tensor& input, const Tensor& target, const std::vector<double>& taps, double c1, double c2,
+          const optional<Tensor>& out, bool mean, const optional<Tensor>& mssim_sum,
+          const optional<Tensor>& num_images) {
+  check_gpu(input, "input");
+  TORCH_CHECK(input.dim() == 4 && input.is_contiguous() && input.numel() > 0,
+              "ssim: input must be a contiguous, non-empty [n, c, h, w] tensor");
+  TORCH_CHECK(target.sizes() == input.sizes() && target.is_contiguous() && target.device() == input.device() &&
+                  target.scalar_type() == input.scalar_type(),
+              "ssim: target must be contiguous with the shape, dtype and device of input");
+  const auto st = input.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16 || st == at::kByte,
+              "ssim: inputs must be float32, float16, bfloat16 or uint8");
+  const int64_t ks = static_cast<int64_t>(taps.size());
+  const int64_t n = input.size(0), c = input.size(1), h = input.size(2), w = input.size(3);
+  TORCH_CHECK(tea::ssim_geometry_ok(n * c, h, w, ks), "ssim: unsupported geometry (odd window of 3..",
+              tea::kSsimMaxKs, " taps no larger than the image, at most ", tea::kSsimMaxPlanes, " planes)");
+  TORCH_CHECK(out.has_value() || mssim_sum.has_value(), "ssim: nothing to write");
+  TORCH_CHECK(mssim_sum.has_value() == num_images.has_value(), "ssim: pass both class states or neither");
+  tea::SsimArgs a;
+  a.x = input.data_ptr();
+  a.y = target.data_ptr();
+  a.dt = dt_of(input);
+  a.n = n;
+  a.c = c;
+  a.h = static_cast<int>(h);
+  a.w = static_cast<int>(w);
+  a.ks = static_cast<int>(ks);
+  for (int64_t j = 0; j < ks; ++j) a.taps[j] = static_cast<float>(taps[j]);
+  a.c1 = static_cast<float>(c1);
+  a.c2 = static_cast<float>(c2);
+  a.mean = mean ? 1 : 0;
+  a.out = f32_out(out, input, mean ? 1 : n, "out");
+  for (const auto* s : {&mssim_sum, &num_images}) {
+    if (!s->has_value()) continue;
+    const Tensor& t = **s;
+    TORCH_CHECK(t.scalar_type() == at::kDouble && t.numel() == 1 && t.device() == input.device(),
+                "ssim: class states must be float64 scalars on the inputs' device");
+  }
+  if (mssim_sum.has_value()) {
+    a.mssim_sum = mssim_sum->data_ptr<double>();
+    a.num_images = num_images->data_ptr<double>();
+  }
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  const hipStream_t stream = stream_for(input);
+  a.partial = static_cast<double*>(scratch_workspace(input, stream, n * c * tea::ssim_tiles(h, w, ks) * 8, 14));
+  check_launch(tea::launch_ssim(a, stream), "ssim");
+}
+
 // FID compute glue (csrc/kernels/fid_prep.hip): FP64 symmetric covariance from the FP32 states.
 void cov_finalize(const Tensor& cov_sum, const Tensor& colsum, double n, const Tensor& out) {
   check_gpu(cov_sum, "cov_sum");
@@ -1871,6 +1921,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cholesky_factor_traced", &cholesky_factor_traced, "K9d with per-column phase stamps (profiling hook)");
   m.def("trapz_sorted", &trapz_sorted, "K3t trapezoid area per row of x-sorted (x, y)", py::arg("x"),
         py::arg("y_bits"), py::arg("out"));
+  m.def("ssim", &ssim, "K12 structural similarity: per-image values or their mean, optional class states",
+        py::arg("input"), py::arg("target"), py::arg("taps"), py::arg("c1"), py::arg("c2"), py::arg("out"),
+        py::arg("mean"), py::arg("mssim_sum") = py::none(), py::arg("num_images") = py::none());
+  m.def("ssim_tile_rows", [] { return tea::kSsimTileH; }, "K12 output tile rows");
+  m.def("ssim_tile_cols", [] { return tea::kSsimTileW; }, "K12 output tile columns");
+  m.def("ssim_max_kernel_size", [] { return tea::kSsimMaxKs; }, "K12 largest native window");
+  m.def("ssim_geometry_ok", &tea::ssim_geometry_ok, "K12 launchable (planes, h, w, kernel_size)");
   m.def("cov_finalize", &cov_finalize, "FP64 symmetric covariance from FP32 FID states",
         py::arg("cov_sum"), py::arg("colsum"), py::arg("n"), py::arg("out"));
   m.def("sym_fill_upper", &sym_fill_upper, "mirror the lower triangle of a float64 matrix into its upper",
@@ -1988,6 +2045,11 @@ void op_cholesky_factor(const Tensor& a, const Tensor& l, const Tensor& linv, co
 void op_potrf_block(const Tensor& a, int64_t k0, int64_t b, const Tensor& linv, const Tensor& info) {
   potrf_block(a, k0, b, linv, info);
 }
+void op_ssim(const Tensor& input, const Tensor& target, at::ArrayRef<double> taps, double c1, double c2,
+             const optional<Tensor>& out, bool mean, const optional<Tensor>& mssim_sum,
+             const optional<Tensor>& num_images) {
+  ssim(input, target, taps.vec(), c1, c2, out, mean, mssim_sum, num_images);
+}
 void op_seg_reduce_rows(const Tensor& rows, const Tensor& out, int64_t ws, at::IntArrayRef offs,
                         at::IntArrayRef counts, at::IntArrayRef dtypes, at::IntArrayRef ops) {
   seg_reduce_rows(rows, out, ws, offs, counts, dtypes, ops);
@@ -2026,6 +2088,8 @@ TORCH_LIBRARY(torcheval_amd, m) {
   m.def("sym_fill_upper(Tensor(a!) m) -> ()");
   m.def("fid_finish(Tensor sum1, float n1, Tensor sum2, float n2, Tensor s1, Tensor s2, Tensor lam, Tensor(a!) out) -> ()");
   m.def("trapz_sorted(Tensor x, Tensor y_bits, Tensor(a!) out) -> ()");
+  m.def("ssim(Tensor input, Tensor target, float[] taps, float c1, float c2, Tensor(a!)? out, bool mean, "
+        "Tensor(b!)? mssim_sum, Tensor(c!)? num_images) -> ()");
   m.def("seg_reduce_rows(Tensor rows, Tensor(a!) out, int ws, int[] offs, int[] counts, int[] dtypes, "
         "int[] ops) -> ()");
   m.def("row_sums(Tensor x, Tensor? t, Tensor? w, float w_scalar, Tensor(a!)[] outs, int[] codes, int rows) -> ()");
@@ -2064,6 +2128,7 @@ TORCH_LIBRARY_IMPL(torcheval_amd, CUDA, m) {
   m.impl("sym_fill_upper", &sym_fill_upper);
   m.impl("fid_finish", &fid_finish);
   m.impl("trapz_sorted", &trapz_sorted);
+  m.impl("ssim", &op_ssim);
   m.impl("seg_reduce_rows", &op_seg_reduce_rows);
   m.impl("row_sums", &op_row_sums);
   m.impl("sort_desc", &op_sort_desc);
@@ -2111,6 +2176,8 @@ TORCH_LIBRARY_IMPL(torcheval_amd, Meta, m) {
   m.impl("fid_finish", [](const Tensor&, double, const Tensor&, double, const Tensor&, const Tensor&, const Tensor&,
                           const Tensor&) {});
   m.impl("trapz_sorted", [](const Tensor&, const Tensor&, const Tensor&) {});
+  m.impl("ssim", [](const Tensor&, const Tensor&, at::ArrayRef<double>, double, double, const optional<Tensor>&, bool,
+                    const optional<Tensor>&, const optional<Tensor>&) {});
   m.impl("seg_reduce_rows", [](const Tensor&, const Tensor&, int64_t, at::IntArrayRef, at::IntArrayRef,
                                at::IntArrayRef, at::IntArrayRef) {});
   m.impl("cls_counts", [](const Tensor&, const Tensor&, int64_t, int64_t, const optional<Tensor>&,

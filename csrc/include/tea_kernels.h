@@ -617,3 +617,31 @@ int launch_publish_words(const int32_t* src, int words, int32_t* slot_dev, int32
                          const int32_t* src2 = nullptr, int words2 = 0);
 int launch_spin_on_flag(const int* flag, int64_t max_ms, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K12: structural similarity of contiguous [n, c, h, w] image pairs (csrc/kernels/ssim.hip).
+// One workgroup per (plane, kSsimTileH x kSsimTileW output tile) writes an FP64 partial; the
+// finish launch turns them into per-image values (or their mean) and the class states.
+constexpr int kSsimTileH = 64;
+constexpr int kSsimTileW = 64;
+constexpr int kSsimMaxKs = 15;
+constexpr int64_t kSsimMaxPlanes = (int64_t{1} << 24) - 1;  // grid.x * 256 threads stays below 2^32
+struct SsimArgs {
+  const void* x = nullptr;
+  const void* y = nullptr;
+  DType dt = DType::f32;  // f32 / f16 / bf16 / u8, both inputs
+  int64_t n = 0, c = 0;
+  int h = 0, w = 0;
+  int ks = 11;                    // odd, 3..kSsimMaxKs
+  float taps[kSsimMaxKs] = {};    // the 1-D window, normalised on the host in FP64
+  float c1 = 0.f, c2 = 0.f;
+  double* partial = nullptr;      // [n * c * ssim_tiles(h, w, ks)] scratch
+  float* out = nullptr;           // [n] values, or [1] mean when ``mean``; may be null
+  int mean = 0;
+  double* mssim_sum = nullptr;    // class states (both or neither): += sum of the n values, += n
+  double* num_images = nullptr;
+};
+int64_t ssim_tiles(int64_t h, int64_t w, int64_t ks);  // output tiles per plane
+bool ssim_geometry_ok(int64_t planes, int64_t h, int64_t w, int64_t ks);
+int launch_ssim(const SsimArgs& a, hipStream_t stream);
+}  // namespace tea

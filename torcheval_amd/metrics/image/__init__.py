@@ -5,8 +5,9 @@ resolves on first access), so importing the metrics package never needs a vision
 """
 
 from torcheval_amd.metrics.image.psnr import PeakSignalNoiseRatio
+from torcheval_amd.metrics.image.ssim import StructuralSimilarity
 
-__all__ = ["FrechetInceptionDistance", "PeakSignalNoiseRatio"]
+__all__ = ["FrechetInceptionDistance", "PeakSignalNoiseRatio", "StructuralSimilarity"]
 __doc_name__ = "Image Metrics"
 
 
