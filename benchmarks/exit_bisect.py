@@ -2,7 +2,7 @@
 selected by argv[1]; prints "done" and exits normally.  Stages:
   import      import torcheval_amd and load _C.so, touch the GPU
   k1          one MulticlassAccuracy update + compute
-  chol        cholesky_ex (K9c potrf blocks + GEMMs) at D=512
+  chol        cholesky_ex (K9d one-launch blocked Cholesky) at D=512
   eig         sym_eigvalsh (K9b cooperative tridiagonalisation + multisection) at D=512
   fid         frechet_distance at D=512 (all of the above)
 """

@@ -1,4 +1,4 @@
-"""Host vs device time of FID compute's blocked Cholesky (K9c + GEMMs) at D = 2048: is the
+"""Host vs device time of FID compute's blocked Cholesky (K9d) at D = 2048: is the
 Python loop the limit?  torch.profiler totals over 10 calls; prints one JSON line."""
 import json
 import os

@@ -1,10 +1,10 @@
 """binary_auroc at N=1M (BASELINE config 3): wall time per call, onesweep sort vs the legacy
 upsweep / downsweep sort (TORCHEVAL_AMD_K3_ONESWEEP=0).  The variable is read once per process,
-so each mode runs in its own child process; one JSON line per mode.  TORCHEVAL_AMD_K3_FOLD=1
-turns on the tile-sum fold into the last onesweep pass (no tile_sums launch); K3_AB_FOLD_PROBE=1
-splits its cost (TORCHEVAL_AMD_K3_FOLD_PROBE: 1 = no atomics, 2 = no fold work).  (Round 5 also measured a
-tile_sums fold into tile_area and counter-ticket tile ids - both slower and removed:
-profiles/k3_onesweep_r5.json.)"""
+so each mode runs in its own child process; one JSON line per mode.  K3_AB_HIST_ROUNDS=1,2,...
+sweeps the histogram block size, K3_AB_ROUNDS=1 adds 16-round tiles.  (Rounds 5 and 6 also
+measured a tile-sum fold into the last pass, a tile_sums fold into tile_area, counter-ticket tile
+ids and a splitter-bucket sort - all slower and removed: profiles/k3_onesweep_r5.json,
+profiles/k3_fold_r5.json, profiles/k3_bucket_attempt_r6.json.)"""
 import json
 import os
 import subprocess
@@ -57,25 +57,17 @@ print(json.dumps(res))
 '''
 
 repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODES = [("1", "", "1"), ("1", "", "0"), ("0", "", "1")]
-if os.environ.get("K3_AB_FOLD_PROBE") == "1":  # fold cost split: no atomics / no fold work at all
-    MODES = [("1", "", "1"), ("1", "", "1p1"), ("1", "", "1p2"), ("1", "", "0")]
+# (onesweep, rounds, histogram rounds)
+MODES = [("1", "", ""), ("0", "", "")]
 HIST = [h for h in os.environ.get("K3_AB_HIST_ROUNDS", "").split(",") if h]
 if HIST:  # histogram blocks of 4096 x h keys (TORCHEVAL_AMD_K3_HIST_ROUNDS), default sort otherwise
-    MODES = [("1", "", "0h" + h) for h in HIST]
+    MODES = [("1", "", h) for h in HIST]
 if os.environ.get("K3_AB_ROUNDS") == "1":
-    MODES += [("1", "16", "1"), ("0", "16", "1")]
-if os.environ.get("K3_AB_BUCKET") == "1":  # splitter-bucket mode (default) vs the four onesweep passes
-    MODES = [("1", "", "0b1"), ("1", "", "0b0"), ("1", "", "0b1"), ("1", "", "0b0")]
-for mode, rounds, fold in MODES:
-    env = dict(os.environ, TORCHEVAL_AMD_K3_ONESWEEP=mode, TORCHEVAL_AMD_K3_ROUNDS=rounds,
-               TORCHEVAL_AMD_K3_FOLD=fold[0], REPO=repo)
-    if fold[1:2] == "p":
-        env["TORCHEVAL_AMD_K3_FOLD_PROBE"] = fold[2:]
-    if fold[1:2] == "h":
-        env["TORCHEVAL_AMD_K3_HIST_ROUNDS"] = fold[2:]
-    if fold[1:2] == "b":
-        env["TORCHEVAL_AMD_K3_BUCKET"] = fold[2:]
+    MODES += [("1", "16", ""), ("0", "16", "")]
+for mode, rounds, hist in MODES:
+    env = dict(os.environ, TORCHEVAL_AMD_K3_ONESWEEP=mode, TORCHEVAL_AMD_K3_ROUNDS=rounds, REPO=repo)
+    if hist:
+        env["TORCHEVAL_AMD_K3_HIST_ROUNDS"] = hist
     out = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=300)
     if out.returncode != 0:
         print(out.stdout[-2000:], out.stderr[-4000:])
@@ -83,9 +75,6 @@ for mode, rounds, fold in MODES:
     line = json.loads(out.stdout.strip().splitlines()[-1])
     line["onesweep"] = mode == "1"
     line["rounds"] = rounds or "default"
-    line["tile_sums_fold"] = fold[0] == "1" and mode == "1"
-    line["fold_probe"] = fold[2:] if fold[1:2] == "p" else None
-    line["hist_rounds"] = fold[2:] if fold[1:2] == "h" else "1"
-    line["bucket"] = fold[2:] != "0" if fold[1:2] == "b" else None
+    line["hist_rounds"] = hist or "1"
     line["n"] = int(os.environ.get("AUROC_N", "1000000"))
     print(json.dumps(line), flush=True)

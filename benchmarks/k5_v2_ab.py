@@ -34,15 +34,10 @@ CONFIGS = [
     {"TORCHEVAL_AMD_K5_V2": "0"},
     {},
     {"TORCHEVAL_AMD_K5_CG": "16", "TORCHEVAL_AMD_K5_BLOCKS": "256"},
-    {"TORCHEVAL_AMD_K5_CG": "16", "TORCHEVAL_AMD_K5_BLOCKS": "256", "TORCHEVAL_AMD_K5_PIPE": "0"},
     {"TORCHEVAL_AMD_K5_CG": "16", "TORCHEVAL_AMD_K5_BLOCKS": "512"},
     {"TORCHEVAL_AMD_K5_CG": "64", "TORCHEVAL_AMD_K5_BLOCKS": "256"},
-    {"TORCHEVAL_AMD_K5_CG": "64", "TORCHEVAL_AMD_K5_BLOCKS": "512"},
-    {"TORCHEVAL_AMD_K5_CG": "16", "TORCHEVAL_AMD_K5_BLOCKS": "256", "TORCHEVAL_AMD_K5_AB_SKIP_FOLD": "1"},
-    {"TORCHEVAL_AMD_K5_CG": "64", "TORCHEVAL_AMD_K5_BLOCKS": "256", "TORCHEVAL_AMD_K5_AB_SKIP_FOLD": "1"},
-    {"TORCHEVAL_AMD_K5_CG": "64", "TORCHEVAL_AMD_K5_BLOCKS": "512", "TORCHEVAL_AMD_K5_AB_SKIP_FOLD": "1"}]
-KNOBS = ("TORCHEVAL_AMD_K5_V2", "TORCHEVAL_AMD_K5_CG", "TORCHEVAL_AMD_K5_BLOCKS", "TORCHEVAL_AMD_K5_MAXR",
-         "TORCHEVAL_AMD_K5_PIPE", "TORCHEVAL_AMD_K5_AB_SKIP_FOLD")
+    {"TORCHEVAL_AMD_K5_CG": "64", "TORCHEVAL_AMD_K5_BLOCKS": "512"}]
+KNOBS = ("TORCHEVAL_AMD_K5_V2", "TORCHEVAL_AMD_K5_CG", "TORCHEVAL_AMD_K5_BLOCKS", "TORCHEVAL_AMD_K5_MAXR")
 
 
 def main() -> None:

@@ -1,4 +1,4 @@
-"""frechet_distance at D = 2048 (K9c blocked Cholesky, L^T S2 L, K9b eigenvalues), 5 calls:
+"""frechet_distance at D = 2048 (K9d blocked Cholesky, L^T S2 L, K9b eigenvalues), 5 calls:
 run under rocprofv3 --kernel-trace --stats."""
 import os
 import sys

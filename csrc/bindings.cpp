@@ -412,17 +412,11 @@ static tea::AucScanArgs scan_args(const Tensor& sorted, const Tensor& order, con
 void auc_scan(const Tensor& sorted, const Tensor& order, const Tensor& target,
               const optional<Tensor>& weight, bool class_mode, const optional<Tensor>& out_auroc,
               const optional<Tensor>& out_auprc, const optional<Tensor>& init,
-              const optional<Tensor>& out_raw, int64_t payload_kind, const optional<Tensor>& tsum) {
+              const optional<Tensor>& out_raw, int64_t payload_kind) {
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sorted.device());
   Tensor tg, w;
   tea::AucScanArgs a = scan_args(sorted, order, target, weight, class_mode, payload_kind, tg, w, "auc_scan");
   const int64_t rows = a.rows, n = a.n;
-  if (tsum.has_value()) {  // tile totals folded by sort_desc (payload kinds 1 / 2 only)
-    TORCH_CHECK(payload_kind != 0 && tsum->scalar_type() == at::kDouble && tsum->is_contiguous() &&
-                    tsum->device() == sorted.device() && tsum->numel() == rows * ((n + 1023) / 1024) * 2,
-                "auc_scan: tsum must be sort_desc's float64 [rows, ceil(n / 1024), 2] fold of a payload sort");
-    a.tsum_ext = tsum->data_ptr<double>();
-  }
   auto f64_out = [&](const optional<Tensor>& t, const char* name) -> double* {
     if (!t.has_value()) return nullptr;
     TORCH_CHECK(t->scalar_type() == at::kDouble && t->is_contiguous() && t->numel() == rows &&
@@ -1198,24 +1192,6 @@ int64_t sym_eigvals(const Tensor& m, const Tensor& lam, const Tensor& status) {
   return 0;
 }
 
-// K9c: one diagonal block of the blocked FP64 Cholesky (factor in place + inverse).
-void potrf_block(const Tensor& a, int64_t k0, int64_t b, const Tensor& linv, const Tensor& info) {
-  check_gpu(a, "matrix");
-  TORCH_CHECK(a.dim() == 2 && a.size(0) == a.size(1) && a.scalar_type() == at::kDouble && a.is_contiguous(),
-              "potrf_block: matrix must be a contiguous float64 [n, n]");
-  TORCH_CHECK(k0 >= 0 && b >= 1 && b <= tea::potrf_block_size() && k0 + b <= a.size(0),
-              "potrf_block: block out of range");
-  TORCH_CHECK(linv.scalar_type() == at::kDouble && linv.is_contiguous() && linv.numel() == b * b &&
-                  linv.device() == a.device(),
-              "potrf_block: linv must be a contiguous float64 [b, b]");
-  TORCH_CHECK(info.scalar_type() == at::kInt && info.numel() >= 1 && info.device() == a.device(),
-              "potrf_block: info must be int32 on the matrix's device");
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
-  check_launch(tea::launch_potrf_block(a.data_ptr<double>(), a.size(1), (int)k0, (int)b, linv.data_ptr<double>(),
-                                       info.data_ptr<int>(), stream_for(a)),
-               "potrf_block");
-}
-
 // K9d: the whole blocked FP64 Cholesky in one persistent launch (csrc/kernels/cholesky.hip).
 // l: padded [64 nt, 64 nt] float64 output (upper triangle zeroed), linv: >= nt * 4096 float64
 // scratch, ctl: >= 1 int32 scratch, status: >= 2 int32 -> [LAPACK info, abort].
@@ -1547,13 +1523,8 @@ uint32_t* onesweep_watch_word(const Tensor& x, hipStream_t st) {
   return it->second;
 }
 
-// `fold` (optional, float64 [rows, ceil(n / 1024), 2]): with a target / label payload on the
-// onesweep path, the last pass also writes the K3 scan's 1024-sample tile totals there
-// (RadixArgs::fold_ab) and the call returns true; pass it to auc_scan as `tsum`.  False: not
-// folded (legacy sort, no payload), auc_scan must run its own tile_sums.
-bool sort_desc(const Tensor& x, const Tensor& out_sorted, const Tensor& out_order,
-               const optional<Tensor>& payload, int64_t payload_kind, const optional<Tensor>& fold,
-               bool ascending = false) {
+void sort_desc(const Tensor& x, const Tensor& out_sorted, const Tensor& out_order,
+               const optional<Tensor>& payload, int64_t payload_kind, bool ascending = false) {
   check_gpu(x, "x");
   TORCH_CHECK(x.dim() == 2 && x.scalar_type() == at::kFloat && x.stride(1) == 1,
               "sort_desc: x must be float32 [rows, n] with contiguous rows");
@@ -1568,17 +1539,16 @@ bool sort_desc(const Tensor& x, const Tensor& out_sorted, const Tensor& out_orde
   a.in_row_stride = x.stride(0);
   a.rows = x.size(0);
   a.n = x.size(1);
-  if (a.rows == 0 || a.n == 0) return false;
+  if (a.rows == 0 || a.n == 0) return;
   a.tiles = tea::radix_sort_tiles(a.rows, a.n);
   const int64_t m = a.rows * a.n;
-  Tensor ws = at::empty({4 * m + a.rows * 256 * a.tiles + a.rows * 512}, x.options().dtype(at::kInt));
+  Tensor ws = at::empty({4 * m + a.rows * 256 * a.tiles}, x.options().dtype(at::kInt));
   uint32_t* base = reinterpret_cast<uint32_t*>(ws.data_ptr<int32_t>());
   a.keys0 = base;
   a.vals0 = base + m;
   a.keys1 = base + 2 * m;
   a.vals1 = base + 3 * m;
   a.hist = base + 4 * m;
-  uint32_t* bkt = a.hist + a.rows * 256 * a.tiles;  // splitter-bucket mode: splitters, bucket sizes
   a.ngroups = tea::radix_sort_groups(a.tiles);
   // self-cleaning: [header: cells left dirty in region 3 | pad | 4 regions of `region` cells]
   int64_t cap = 0;
@@ -1631,8 +1601,6 @@ bool sort_desc(const Tensor& x, const Tensor& out_sorted, const Tensor& out_orde
     a.os_splane = scap / 8;  // two u32 planes
     a.os_gacc = gws;
     a.os_gplane = gcap / 16;  // two u64 planes
-    a.bkt_spl = bkt;
-    a.bkt_cnt = bkt + a.rows * 256;
     a.os_watch = onesweep_watch_word(x, st);
   }
   Tensor pl;
@@ -1659,23 +1627,7 @@ bool sort_desc(const Tensor& x, const Tensor& out_sorted, const Tensor& out_orde
     a.payload = pl.data_ptr();
     a.payload_dt = dt_of(pl);
   }
-  const int64_t otiles = (a.n + 1023) / 1024;
-  if (fold.has_value()) {
-    TORCH_CHECK(fold->scalar_type() == at::kDouble && fold->is_contiguous() && fold->device() == x.device() &&
-                    fold->numel() == a.rows * otiles * 2,
-                "sort_desc: fold must be contiguous float64 [rows, ceil(n / 1024), 2] on the device of x");
-    if (a.os_hdr != nullptr && a.payload_kind != 0) {
-      a.fold_ab = fold->data_ptr<double>();
-      a.fold_otiles = otiles;
-      static const int probe = [] {
-        const char* e = std::getenv("TORCHEVAL_AMD_K3_FOLD_PROBE");
-        return e ? std::atoi(e) : 0;
-      }();
-      a.fold_probe = probe;
-    }
-  }
   check_launch(tea::launch_radix_sort_desc(a, stream_for(x)), "sort_desc");
-  return a.fold_ab != nullptr;
 }
 
 
@@ -1839,7 +1791,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("auc_scan", &auc_scan, "K3 tie-aware scan -> AUROC / AUPRC per row", py::arg("sorted"),
         py::arg("order"), py::arg("target"), py::arg("weight"), py::arg("class_mode"),
         py::arg("out_auroc"), py::arg("out_auprc"), py::arg("init") = py::none(),
-        py::arg("out_raw") = py::none(), py::arg("payload_kind") = 0, py::arg("tsum") = py::none());
+        py::arg("out_raw") = py::none(), py::arg("payload_kind") = 0);
   m.def("curve_workspace_bytes", &curve_workspace_bytes, "K3c workspace bytes", py::arg("rows"), py::arg("n"),
         py::arg("rafp"));
   m.def("curve_count", &curve_count, "K3c tile totals + tie-group tails + per-row scans (G_r -> sizes)",
@@ -1899,16 +1851,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x"), pybind11::arg("clear") = true);
   m.def("sort_desc", &sort_desc, "K3a segmented stable radix sort, descending or ascending (f32 -> sorted, int32 order)",
         py::arg("x"), py::arg("out_sorted"), py::arg("out_order"), py::arg("payload") = py::none(),
-        py::arg("payload_kind") = 0, py::arg("fold") = py::none(), py::arg("ascending") = false);
+        py::arg("payload_kind") = 0, py::arg("ascending") = false);
   m.def("binned_finalize", &binned_finalize, "binned AUROC / AUPRC / PR-curve points from counts",
         py::arg("tp"), py::arg("fp"), py::arg("fn") = py::none(), py::arg("out_auroc") = py::none(),
         py::arg("out_auprc") = py::none(), py::arg("out_prec") = py::none(),
         py::arg("out_rec") = py::none());
   m.def("fid_cov_update", &fid_cov_update, "K8 FP32-MFMA symmetric rank-k covariance update",
         py::arg("act"), py::arg("cov"), py::arg("colsum"));
-  m.def("potrf_block", &potrf_block, "K9c diagonal-block FP64 Cholesky + inverse (blocked Cholesky step)",
-        py::arg("a"), py::arg("k0"), py::arg("b"), py::arg("linv"), py::arg("info"));
-  m.def("potrf_block_size", &tea::potrf_block_size, "K9c block size");
   m.def("cholesky_factor", &cholesky_factor, "K9d one-launch blocked FP64 Cholesky (padded factor, info, abort)",
         py::arg("a"), py::arg("l"), py::arg("linv"), py::arg("ctl"), py::arg("status"));
   m.def("cholesky_tiles", &tea::cholesky_tiles, "K9d 64 x 64 tiles per side");
@@ -1954,12 +1903,12 @@ void op_row_sums(const Tensor& x, const optional<Tensor>& t, const optional<Tens
 }
 void op_sort_desc(const Tensor& x, const Tensor& s, const Tensor& o, const optional<Tensor>& p, int64_t kind,
                   bool ascending) {
-  sort_desc(x, s, o, p, kind, c10::nullopt, ascending);
+  sort_desc(x, s, o, p, kind, ascending);
 }
 void op_auc_scan(const Tensor& sorted, const Tensor& order, const Tensor& target, const optional<Tensor>& weight,
                  bool class_mode, const optional<Tensor>& out_auroc, const optional<Tensor>& out_auprc,
                  const optional<Tensor>& init, const optional<Tensor>& out_raw, int64_t payload_kind) {
-  auc_scan(sorted, order, target, weight, class_mode, out_auroc, out_auprc, init, out_raw, payload_kind, c10::nullopt);
+  auc_scan(sorted, order, target, weight, class_mode, out_auroc, out_auprc, init, out_raw, payload_kind);
 }
 void op_rafp(const Tensor& sorted, const Tensor& order, const Tensor& target, bool class_mode, int64_t kind,
              double p, const Tensor& out_rec, const Tensor& out_thr) {
@@ -2042,9 +1991,6 @@ int64_t op_sym_eigvals(const Tensor& m, const Tensor& lam, const Tensor& status)
 void op_cholesky_factor(const Tensor& a, const Tensor& l, const Tensor& linv, const Tensor& ctl, const Tensor& status) {
   cholesky_factor(a, l, linv, ctl, status);
 }
-void op_potrf_block(const Tensor& a, int64_t k0, int64_t b, const Tensor& linv, const Tensor& info) {
-  potrf_block(a, k0, b, linv, info);
-}
 void op_ssim(const Tensor& input, const Tensor& target, at::ArrayRef<double> taps, double c1, double c2,
              const optional<Tensor>& out, bool mean, const optional<Tensor>& mssim_sum,
              const optional<Tensor>& num_images) {
@@ -2081,7 +2027,6 @@ TORCH_LIBRARY(torcheval_amd, m) {
   m.def("binned_finalize(Tensor tp, Tensor fp, Tensor? fn, Tensor(a!)? out_auroc, Tensor(b!)? out_auprc, "
         "Tensor(c!)? out_prec, Tensor(d!)? out_rec) -> ()");
   m.def("sym_eigvals(Tensor m, Tensor(a!) lam, Tensor(b!) status) -> int");
-  m.def("potrf_block(Tensor(a!) a, int k0, int b, Tensor(b!) linv, Tensor(c!) info) -> ()");
   m.def("cholesky_factor(Tensor a, Tensor(a!) l, Tensor(b!) linv, Tensor(c!) ctl, Tensor(d!) status) -> ()");
   m.def("pivchol(Tensor a, Tensor(a!) slots, Tensor(b!) w, Tensor(c!) piv, Tensor(d!) info, Tensor(e!) ctl) -> int");
   m.def("cov_finalize(Tensor cov_sum, Tensor colsum, float n, Tensor(a!) out) -> ()");
@@ -2121,7 +2066,6 @@ TORCH_LIBRARY_IMPL(torcheval_amd, CUDA, m) {
   m.impl("multilabel_counts", &op_multilabel_counts);
   m.impl("binned_finalize", &op_binned_finalize);
   m.impl("sym_eigvals", &op_sym_eigvals);
-  m.impl("potrf_block", &op_potrf_block);
   m.impl("cholesky_factor", &op_cholesky_factor);
   m.impl("cov_finalize", &cov_finalize);
   m.impl("pivchol", &pivchol);
@@ -2166,7 +2110,6 @@ TORCH_LIBRARY_IMPL(torcheval_amd, Meta, m) {
                                  const optional<Tensor>&, double) {});
   m.impl("binned_finalize", [](const Tensor&, const Tensor&, const optional<Tensor>&, const optional<Tensor>&,
                                const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {});
-  m.impl("potrf_block", [](const Tensor&, int64_t, int64_t, const Tensor&, const Tensor&) {});
   m.impl("cholesky_factor", [](const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {});
   m.impl("cov_finalize", [](const Tensor&, const Tensor&, double, const Tensor&) {});
   m.impl("pivchol", [](const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&) {

@@ -115,7 +115,6 @@ struct AucScanArgs {
   // workspace carve-up (set by the launcher)
   void* ab = nullptr;
   void* tsum = nullptr;
-  const void* tsum_ext = nullptr;  // [rows, ntiles] D2 tile totals already folded by the sort
   void* tstart = nullptr;
   void* tarea = nullptr;
   void* totals = nullptr;
@@ -240,13 +239,11 @@ struct MomentsArgs {
   int v2_cg = 0;                // column groups (of 4) per tile: 4 / 16 / 64; 0 = two-launch form
   int v2_r = 0;                 // row chunks per tile
   int64_t v2_chunk = 0;         // rows per chunk
-  int v2_pipe = 0;              // two batches of loads in flight per thread (0: one)
   // deferred mode (class updates): each block ADDS its FP64 column partials to its own slot of
   // pend ([slots][ns][d] then [slots] weight totals / row counts) and the launch ends there;
   // launch_moments_fold folds the slots into the float32 states when they are read
   double* pend = nullptr;
   int pend_slots = 0;
-  int v2_skip_fold = 0;         // A/B only: stop after the partial stores (results invalid)
 };
 int column_moments_blocks(int64_t n, int64_t d);
 // v2 plan: whether it applies, and its geometry / workspace size (doubles and tickets)
@@ -483,22 +480,10 @@ struct RadixArgs {
   int64_t os_splane = 0;          // words per status plane
   unsigned long long* os_gacc = nullptr;  // 2 planes of [rows * ngroups, 256] (arrivals << 32 | sum)
   int64_t os_gplane = 0;          // words per group plane
-  // optional K3 tile-sum fold (onesweep, payload kinds 1 / 2): the last pass adds each
-  // 1024-sample output tile's (sum a, sum b) of the sorted payload (a = t, b = 1 - t; kind 2:
-  // t = [label == row]) into fold_ab, which pass 0 zeroes; auc_scan then skips tile_sums
-  double* fold_ab = nullptr;      // [rows, fold_otiles, 2]
-  int64_t fold_otiles = 0;        // ceil(n / 1024)
-  int fold_probe = 0;             // A/B probe (TORCHEVAL_AMD_K3_FOLD_PROBE): 1 no atomics, 2 no fold work
   // 0: descending (NaN first); ~0u: ascending (NaN last, as torch.sort ascending), both stable -
   // XORed into every key at load and out of it at the final store
   uint32_t key_xor = 0;
-  // splitter-bucket mode (radix_bucket_ok; onesweep workspaces required): 255 equal-frequency
-  // splitters per row from a sorted sample, ONE stable onesweep pass scatters the keys into the
-  // 256 buckets they delimit, and one workgroup per bucket finishes it in LDS
-  uint32_t* bkt_spl = nullptr;  // [rows, 256] splitters (sample kernel)
-  uint32_t* bkt_cnt = nullptr;  // [rows, 256] bucket sizes (the pass's first tile)
 };
-bool radix_bucket_ok(int64_t rows, int64_t n);    // the rows / lengths the bucket mode takes
 bool radix_onesweep_ok(int64_t rows, int64_t n);  // the tiling the onesweep passes take
 int64_t radix_onesweep_status_words(int64_t rows, int64_t n);
 int64_t radix_onesweep_group_words(int64_t rows, int64_t n);
@@ -556,10 +541,6 @@ int launch_symeig(const SymEigArgs& a, hipStream_t stream);
 }  // namespace tea
 
 namespace tea {
-// K9c: factor the b x b diagonal block A[k0:k0+b, k0:k0+b] (row-major, leading dimension lda)
-// in place into its lower Cholesky factor (upper part zeroed) and write its inverse to Linv
-// [b, b]; a non-positive pivot sets *info = k0 + column + 1 (if still 0).  b <= 64.
-int potrf_block_size();
 // K9d (cholesky.hip): the whole blocked Cholesky in one persistent launch.  L: padded
 // [64 nt, 64 nt] factor, Linv: nt x 64 x 64, ctl: 1 int (ticket), status: 2 ints (info, abort)
 int cholesky_tiles(int64_t n);
@@ -577,7 +558,6 @@ int launch_fid_finish(const float* sum1, double n1, const float* sum2, double n2
                       hipStream_t stream);
 int launch_cholesky(const double* A, int64_t lda, int64_t n, double* L, double* Linv, int* ctl, int* status,
                     hipStream_t stream, unsigned long long* trace = nullptr);
-int launch_potrf_block(double* A, int64_t lda, int k0, int b, double* Linv, int* info, hipStream_t stream);
 // K9p (pivchol.hip): pivoted FP64 Cholesky, one cooperative launch.  slots: pivchol_slot_words(n)
 // 64-bit words, w: [N, N] doubles, N = pivchol_padded(n); info {rank, status}; ctl 1 word.
 // 0 launched, 3 not co-schedulable, 4 n unsupported

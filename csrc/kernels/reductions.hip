@@ -465,7 +465,7 @@ __device__ __forceinline__ float mse_den(double w_tot) {
   return fmaxf(fabsf(sw), eps) * sgn;
 }
 
-template <int CG, int NEED, bool HAS_W, bool PIPE>
+template <int CG, int NEED, bool HAS_W>
 __global__ __launch_bounds__(kB) void moments_v2_kernel(MomentsArgs a) {
   using NI = NeedInfo<NEED>;
   constexpr int RPP = kB / CG, TC = CG * 4, NS = NI::ns, TP = kB / TC;
@@ -495,27 +495,10 @@ __global__ __launch_bounds__(kB) void moments_v2_kernel(MomentsArgs a) {
   constexpr int64_t kStep = static_cast<int64_t>(RPP) * kU2;
   int64_t i = r0 + rl;
   if (active && i < r1) {
-    if constexpr (PIPE) {
-      // two batches in flight: the next batch's loads are issued before this one is consumed
-      V2Batch<NEED, HAS_W> b0, b1;
-      b0.load(xp, tp, wp, xrs, trs, a.w_stride, i, r1, RPP);
-      for (;;) {
-        const int64_t i1 = i + kStep;
-        if (i1 < r1) b1.load(xp, tp, wp, xrs, trs, a.w_stride, i1, r1, RPP);
-        b0.accumulate(acc, wsum, i, r1, RPP);
-        if (i1 >= r1) break;
-        const int64_t i2 = i1 + kStep;
-        if (i2 < r1) b0.load(xp, tp, wp, xrs, trs, a.w_stride, i2, r1, RPP);
-        b1.accumulate(acc, wsum, i1, r1, RPP);
-        if (i2 >= r1) break;
-        i = i2;
-      }
-    } else {
-      for (; i < r1; i += kStep) {
-        V2Batch<NEED, HAS_W> b;
-        b.load(xp, tp, wp, xrs, trs, a.w_stride, i, r1, RPP);
-        b.accumulate(acc, wsum, i, r1, RPP);
-      }
+    for (; i < r1; i += kStep) {
+      V2Batch<NEED, HAS_W> b;
+      b.load(xp, tp, wp, xrs, trs, a.w_stride, i, r1, RPP);
+      b.accumulate(acc, wsum, i, r1, RPP);
     }
   }
   // row lanes -> LDS at the columns' tile positions (the tail group's first sh lanes are
@@ -632,7 +615,6 @@ __global__ __launch_bounds__(kB) void moments_v2_kernel(MomentsArgs a) {
     for (int r = 0; r < RPP; ++r) v += lds_w[r];
     wt_store(wpart + static_cast<int64_t>(tile) * R + rc, v);
   }
-  if (a.v2_skip_fold) return;  // A/B only (benchmarks/k5_v2_ab.py): the streaming part alone
   if (!wt_arrive_last(a.tickets + tile, static_cast<unsigned>(R))) return;
 
   // ---- the tile's last block: TP threads per column each sum a strided share of the R
@@ -766,18 +748,17 @@ __global__ __launch_bounds__(kB) void moments_pend_fold_kernel(MomentsArgs a, in
   }
 }
 
-template <int CG, int NEED, bool PIPE>
+template <int CG, int NEED>
 void launch_v2_w(const MomentsArgs& a, dim3 grid, hipStream_t stream) {
-  if (a.w) hipLaunchKernelGGL((moments_v2_kernel<CG, NEED, true, PIPE>), grid, dim3(kB), 0, stream, a);
-  else hipLaunchKernelGGL((moments_v2_kernel<CG, NEED, false, PIPE>), grid, dim3(kB), 0, stream, a);
+  if (a.w) hipLaunchKernelGGL((moments_v2_kernel<CG, NEED, true>), grid, dim3(kB), 0, stream, a);
+  else hipLaunchKernelGGL((moments_v2_kernel<CG, NEED, false>), grid, dim3(kB), 0, stream, a);
 }
 
 template <int NEED>
 void launch_v2_need(const MomentsArgs& a, dim3 grid, hipStream_t stream) {
-  const bool pipe = a.v2_pipe != 0;
-  if (a.v2_cg == 4) pipe ? launch_v2_w<4, NEED, true>(a, grid, stream) : launch_v2_w<4, NEED, false>(a, grid, stream);
-  else if (a.v2_cg == 16) pipe ? launch_v2_w<16, NEED, true>(a, grid, stream) : launch_v2_w<16, NEED, false>(a, grid, stream);
-  else pipe ? launch_v2_w<64, NEED, true>(a, grid, stream) : launch_v2_w<64, NEED, false>(a, grid, stream);
+  if (a.v2_cg == 4) launch_v2_w<4, NEED>(a, grid, stream);
+  else if (a.v2_cg == 16) launch_v2_w<16, NEED>(a, grid, stream);
+  else launch_v2_w<64, NEED>(a, grid, stream);
 }
 
 int need_of(const MomentsArgs& a) {
@@ -894,14 +875,12 @@ int env_read(const char* name, int dflt) {
 // K5 geometry knobs: read once, or on every call when TORCHEVAL_AMD_AB_DYNAMIC=1 (A/B
 // harnesses switch them inside one process)
 struct K5Knobs {
-  int v2, cg, blocks, maxr, pipe, skip;
+  int v2, cg, blocks, maxr;
   void read() {
     v2 = env_read("TORCHEVAL_AMD_K5_V2", 1);
     cg = env_read("TORCHEVAL_AMD_K5_CG", 0);
     blocks = env_read("TORCHEVAL_AMD_K5_BLOCKS", 0);
     maxr = env_read("TORCHEVAL_AMD_K5_MAXR", 64);
-    pipe = env_read("TORCHEVAL_AMD_K5_PIPE", 0);
-    skip = env_read("TORCHEVAL_AMD_K5_AB_SKIP_FOLD", 0);
   }
 };
 const K5Knobs& k5_knobs() {
@@ -944,8 +923,6 @@ bool column_moments_v2_plan(MomentsArgs& a, int64_t* ws_doubles, int64_t* ticket
   if (r > 65535 || tiles > 65535) return false;
   const int ns = need == 1 ? 1 : need == 7 ? 3 : 4;
   a.v2_cg = cg;
-  a.v2_pipe = kn.pipe != 0;
-  a.v2_skip_fold = kn.skip != 0;
   a.v2_r = static_cast<int>(r);
   a.v2_chunk = chunk;
   // partials [tiles][ns][R][tc], weights [tiles][R], scalars max(4 per tile, 2 per block)

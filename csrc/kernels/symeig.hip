@@ -553,255 +553,6 @@ __global__ __launch_bounds__(NT) void tridiag_kernel(const double* __restrict__ 
   }
 }
 
-// ---------------------------------------------------------------- K9b v2: rows per WAVE
-// The same one-launch Householder reduction with a different ownership: each WAVE holds kRW
-// whole rows (lane l: columns l + 64 s, s < C), so every reduction of a column step is a
-// wave reduction (DPP inside 16-lane rows + 4 readlanes) instead of a block reduction with an
-// LDS round trip and a barrier.  The per-column phase trace of tridiag_kernel
-// (csrc/bench/k9b_trace.hip, round 5) spent ~8.9k of ~15.7k cycles per column in its three
-// block reductions, the reflector and the pass; the hand-off wait was the other ~6.8k.  Per
-// column here: the workgroup stages the handed-off p_j and row j+1 in LDS (one barrier,
-// double-buffered by column parity), then each wave redundantly forms w_j, updates row j+1,
-// derives reflector j+1 and applies step j to its rows while accumulating p_{j+1} - no further
-// barrier.  Hand-off slots, sentinel protocol, abort word and outputs are tridiag_kernel's.
-// Measured (round 5, profiles/symeig_wave_ab_r5.json): exact (the K9b tests pass with it), but
-// 18.5 ms at D = 2048 against tridiag_kernel's 14.7 ms - every wave redoes the column-length
-// work (R1, the row j+1 update, the reflector: 32 elements per lane instead of 8) and at one
-// wave per SIMD nothing hides the dependent DPP / readlane chains - so it is opt-in.
-constexpr int kRW = 2;                // rows per wave
-constexpr int kWRows = kRW * kWaves;  // rows per workgroup
-
-__device__ __forceinline__ double readlane_d(double x, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-
-// the wave's total in every lane, fixed order (deterministic)
-__device__ __forceinline__ double wave_sum_d(double x) {
-  x = row16_sum(x);
-  return (readlane_d(x, 15) + readlane_d(x, 31)) + (readlane_d(x, 47) + readlane_d(x, 63));
-}
-
-// LAPACK dlarfg on x = a[jj+1 .. n) with the diagonal a[jj]; `alpha`, `diag` broadcast by the
-// caller; returns tau / beta / scale (v[jj+1] = 1, v[k] = a[k] * scale beyond)
-__device__ __forceinline__ Reflector reflector_of(double alpha, double sigma, double diag) {
-  Reflector h;
-  h.diag = diag;
-  if (sigma == 0.0) {
-    h.tau = 0.0;
-    h.beta = alpha;
-    h.scale = 0.0;
-  } else {
-    const double mu = sqrt(alpha * alpha + sigma);
-    h.beta = alpha >= 0.0 ? -mu : mu;
-    h.tau = (h.beta - alpha) / h.beta;
-    h.scale = 1.0 / (alpha - h.beta);
-  }
-  return h;
-}
-
-template <int C>
-__global__ __launch_bounds__(kThreads, 1) void tridiag_wave_kernel(const double* __restrict__ A, int n, int64_t ld,
-                                                                    double* d_out, double* e_out,
-                                                                    unsigned long long* slots, unsigned* ctl) {
-  constexpr int kCols = C * 64;
-  constexpr int kQ = kCols / kThreads;  // staged slots per thread per plane
-  __shared__ double sp[2][kCols];       // p_j, by column parity
-  __shared__ double sr[2][kCols];       // row j+1 (updated through step j-1)
-  const int64_t plane = (int64_t)(n - 2) * ld;
-  unsigned long long* const gp0 = slots;
-  unsigned long long* const gr0 = slots + plane;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int row0 = blockIdx.x * kWRows + wv * kRW;  // this wave's first row
-  // registers: the wave's rows, v_j and a (row j+1, turned into v_{j+1} in place); w_j is
-  // re-formed from the staged p_j where it is needed (register pressure: 4 x C doubles)
-  double rw[kRW][C];
-#pragma unroll
-  for (int r = 0; r < kRW; ++r)
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const int k = lane + 64 * s, row = row0 + r;
-      rw[r][s] = (row < n && k < n) ? A[(int64_t)row * n + k] : 0.0;
-    }
-  double v[C], a[C];
-
-  // ---- phase 0: reflector 0 from row 0, p_0 of the wave's rows, row 1 published as is
-  Reflector h;
-  {
-    double s2 = 0.0, alpha = 0.0, diag = 0.0;
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const int k = lane + 64 * s;
-      a[s] = k < n ? A[k] : 0.0;
-      s2 += k >= 2 ? a[s] * a[s] : 0.0;
-      alpha = k == 1 ? a[s] : alpha;
-      diag = k == 0 ? a[s] : diag;
-    }
-    h = reflector_of(readlane_d(alpha, 1), wave_sum_d(s2), readlane_d(diag, 0));
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const int k = lane + 64 * s;
-      v[s] = k == 1 ? 1.0 : (k >= 2 ? a[s] * h.scale : 0.0);
-    }
-    if (blockIdx.x == 0 && t == 0) {
-      d_out[0] = h.diag;
-      e_out[0] = h.beta;
-    }
-#pragma unroll
-    for (int r = 0; r < kRW; ++r) {
-      double acc = 0.0;
-#pragma unroll
-      for (int s = 0; s < C; ++s) acc += rw[r][s] * v[s];
-      acc = wave_sum_d(acc);
-      const int row = row0 + r;
-      if (lane == 0 && row < n && row >= 1) put(gp0, row, h.tau * acc);
-    }
-    if (row0 <= 1 && 1 < row0 + kRW) {
-#pragma unroll
-      for (int s = 0; s < C; ++s) {
-        const int k = lane + 64 * s;
-        if (k >= 1 && k < n) put(gr0, k, row0 == 1 ? rw[0][s] : rw[1][s]);
-      }
-    }
-  }
-
-  for (int j = 0; j <= n - 3; ++j) {
-    // ---- stage p_j and row j+1 in LDS (dead / padded columns as zeros); bounded spin
-    unsigned long long* const gp = gp0 + (int64_t)j * ld;
-    unsigned long long* const gr = gr0 + (int64_t)j * ld;
-    double* const P = sp[j & 1];
-    double* const R = sr[j & 1];
-    bool aborted = false;
-    for (unsigned spins = 0;; ++spins) {
-      const unsigned abort_word = __hip_atomic_load((gu32*)&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      bool ok = true;
-#pragma unroll
-      for (int q = 0; q < kQ; ++q) {
-        const int k = t + kThreads * q;
-        if (k >= j + 1 && k < n) {
-          const unsigned long long x0 = get(gp + k), y0 = get(gr + k);
-          ok = ok && x0 != kSentBits && y0 != kSentBits;
-          P[k] = as_double(x0);
-          R[k] = as_double(y0);
-        } else {
-          P[k] = 0.0;
-          R[k] = 0.0;
-        }
-      }
-      if (ok) break;
-      if (abort_word != 0u) {
-        aborted = true;
-        break;
-      }
-      if (spins > kSpinLimit) {
-        __hip_atomic_store((gu32*)&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        aborted = true;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (__syncthreads_or(aborted)) return;
-
-    // ---- w_j = p_j - c v_j, row j+1 <- row j+1 - v_j[j+1] w_j - w_j[j+1] v_j (every wave)
-    double r1 = 0.0;
-#pragma unroll
-    for (int s = 0; s < C; ++s) r1 += P[lane + 64 * s] * v[s];
-    r1 = wave_sum_d(r1);
-    const double c = 0.5 * h.tau * r1;
-    const double wj1 = P[j + 1] - c;  // v_j[j+1] = 1
-    double vi0 = 0.0, vi1 = 0.0, a1 = 0.0, a2 = 0.0, s2 = 0.0;
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const int k = lane + 64 * s;
-      const double ws = P[k] - c * v[s];
-      a[s] = R[k] - (ws + wj1 * v[s]);
-      vi0 = k == row0 ? v[s] : vi0;
-      vi1 = k == row0 + 1 ? v[s] : vi1;
-      a1 = k == j + 1 ? a[s] : a1;
-      a2 = k == j + 2 ? a[s] : a2;
-      s2 += k >= j + 3 ? a[s] * a[s] : 0.0;
-    }
-    // the wave's rows' v_j[i] (lane i & 63 holds them), w_j[i] from the staged p_j
-    double vi[kRW], wi[kRW];
-    vi[0] = row0 < n ? readlane_d(vi0, row0 & 63) : 0.0;
-    vi[1] = row0 + 1 < n ? readlane_d(vi1, (row0 + 1) & 63) : 0.0;
-    wi[0] = row0 < n ? P[row0] - c * vi[0] : 0.0;
-    wi[1] = row0 + 1 < n ? P[row0 + 1] - c * vi[1] : 0.0;
-    a1 = readlane_d(a1, (j + 1) & 63);
-
-    if (j == n - 3) {
-      // last step: row n-2 is final; the owner of row n-1 finishes its diagonal
-      if (blockIdx.x == 0 && wv == 0) {
-#pragma unroll
-        for (int s = 0; s < C; ++s) {
-          const int k = lane + 64 * s;
-          if (k == n - 2) d_out[n - 2] = a[s];
-          if (k == n - 1) e_out[n - 2] = a[s];
-        }
-      }
-      const int r = (n - 1) - row0;
-      if (r >= 0 && r < kRW) {
-#pragma unroll
-        for (int s = 0; s < C; ++s) {
-          const int k = lane + 64 * s;
-          if (k == n - 1) d_out[n - 1] = (r == 0 ? rw[0][s] : rw[1][s]) - 2.0 * vi[r] * wi[r];
-        }
-      }
-      break;
-    }
-
-    // ---- reflector j+1 (redundant in every wave); a becomes v_{j+1}
-    a2 = readlane_d(a2, (j + 2) & 63);
-    const Reflector hn = reflector_of(a2, wave_sum_d(s2), a1);
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const int k = lane + 64 * s;
-      a[s] = k == j + 2 ? 1.0 : (k >= j + 3 ? a[s] * hn.scale : 0.0);
-    }
-    if (blockIdx.x == 0 && t == 0) {
-      d_out[j + 1] = hn.diag;
-      e_out[j + 1] = hn.beta;
-    }
-
-    // ---- one register pass: step j on the wave's rows, p_{j+1} accumulated
-    double acc[kRW] = {0.0, 0.0};
-    const bool live0 = row0 < n && row0 >= j + 1, live1 = row0 + 1 < n && row0 + 1 >= j + 1;  // wave-uniform
-#pragma unroll
-    for (int s = 0; s < C; ++s) {
-      const double ws = P[lane + 64 * s] - c * v[s];
-      if (live0) {
-        const double x = rw[0][s] - (vi[0] * ws + wi[0] * v[s]);
-        rw[0][s] = x;
-        acc[0] += x * a[s];
-      }
-      if (live1) {
-        const double x = rw[1][s] - (vi[1] * ws + wi[1] * v[s]);
-        rw[1][s] = x;
-        acc[1] += x * a[s];
-      }
-    }
-    // the owner of row j+2 publishes the row before the p reduction
-    const int ro = (j + 2) - row0;
-    if (ro >= 0 && ro < kRW) {
-#pragma unroll
-      for (int s = 0; s < C; ++s) {
-        const int k = lane + 64 * s;
-        if (k >= j + 2 && k < n) put(gr0 + (int64_t)(j + 1) * ld, k, ro == 0 ? rw[0][s] : rw[1][s]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kRW; ++r) {
-      const double pt = wave_sum_d(acc[r]);
-      const int row = row0 + r;
-      if (lane == 0 && row < n && row >= j + 2) put(gp0 + (int64_t)(j + 1) * ld, row, hn.tau * pt);
-    }
-#pragma unroll
-    for (int s = 0; s < C; ++s) v[s] = a[s];
-    h = hn;
-  }
-}
-
 // The reduction's last kTail columns on one workgroup (LAPACK dsytd2 on the trailing block),
 // the block held in registers: TR x 8 tiles, 16 tile columns, kTail / TR tile rows, one thread a
 // tile (thread t: tile row t / 16, tile column t % 16; a 16-lane DPP row = one tile row).  Per
@@ -1194,28 +945,6 @@ int64_t symeig_slot_bytes(int64_t n) { return 2 * (n - 2) * symeig_slot_stride(n
 int launch_symeig(const SymEigArgs& a, hipStream_t stream) {
   int G = 0, R = 0;
   if (symeig_plan(a.n, &G, &R) != 0) return 1;
-  // K9b v2 (rows per wave) only on TORCHEVAL_AMD_SYMEIG_WAVE=1, and only when the grid of
-  // n / 8 workgroups fits the device's CUs and the row fits 32 columns per lane (n <= 2048):
-  // measured slower than tridiag_kernel (18.5 vs 14.7 ms at D = 2048,
-  // profiles/symeig_wave_ab_r5.json), kept as the A/B arm
-  static const bool wave_mode = [] {
-    const char* e = std::getenv("TORCHEVAL_AMD_SYMEIG_WAVE");
-    return e && e[0] == '1';
-  }();
-  const void* wkern = nullptr;
-  int GW = 0;
-  if (wave_mode && a.n <= 2048) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        (a.n + kWRows - 1) / kWRows <= cus) {
-      GW = (int)((a.n + kWRows - 1) / kWRows);
-      wkern = a.n <= 512    ? reinterpret_cast<const void*>(&tridiag_wave_kernel<8>)
-              : a.n <= 1024 ? reinterpret_cast<const void*>(&tridiag_wave_kernel<16>)
-              : a.n <= 1536 ? reinterpret_cast<const void*>(&tridiag_wave_kernel<24>)
-                            : reinterpret_cast<const void*>(&tridiag_wave_kernel<32>);
-    }
-  }
   // the smallest instance holding ceil(n / 256) columns and R rows per thread: every register
   // slot is live (the pass has no per-element column test), e.g. 8 x 8 for the FID's D = 2048
   const int need = (int)max((a.n + kThreads - 1) / kThreads, (int64_t)R);
@@ -1272,9 +1001,8 @@ int launch_symeig(const SymEigArgs& a, hipStream_t stream) {
     return !(e && e[0] == '0');
   }();
   double* tail = a.tail;
-  int jt = (tail_on && tail != nullptr && !wkern && n >= 2 * kTail) ? n - kTail : n;
+  int jt = (tail_on && tail != nullptr && n >= 2 * kTail) ? n - kTail : n;
   void* args[] = {&A, &n, &R, &ld, &d, &e, &slots, &ctl, &tail, &jt};
-  void* wargs[] = {&A, &n, &ld, &d, &e, &slots, &ctl};
   // TORCHEVAL_AMD_SYMEIG_COOP=0: a plain launch of the same grid (A/B of the cooperative
   // launch's process-exit behaviour under rocprofv3; G <= #CUs workgroups are co-resident in
   // practice and the bounded hand-off spins abort to the library fallback if they are not)
@@ -1282,12 +1010,8 @@ int launch_symeig(const SymEigArgs& a, hipStream_t stream) {
     const char* e = std::getenv("TORCHEVAL_AMD_SYMEIG_COOP");
     return !(e && e[0] == '0');
   }();
-  const void* lk = wkern ? wkern : kern;
-  void** la = wkern ? wargs : args;
-  const int lg = wkern ? GW : G;
-  const int lt = wkern ? kThreads : nt;
-  const hipError_t lrc = coop ? hipLaunchCooperativeKernel(lk, dim3(lg), dim3(lt), la, 0, stream)
-                              : hipLaunchKernel(lk, dim3(lg), dim3(lt), la, 0, stream);
+  const hipError_t lrc = coop ? hipLaunchCooperativeKernel(kern, dim3(G), dim3(nt), args, 0, stream)
+                              : hipLaunchKernel(kern, dim3(G), dim3(nt), args, 0, stream);
   if (lrc != hipSuccess) return 3;
   // tile height: TORCHEVAL_AMD_SYMEIG_TAIL_TR=8 (256 threads, the default) / 4 (512) / 2 (1024):
   // 210 / 217 / 280 us at D = 2048 (profiles/k9b_tail_r6.json)
@@ -1319,137 +1043,6 @@ int launch_symeig(const SymEigArgs& a, hipStream_t stream) {
     tridiag_eigvals_kernel<32><<<(n + kWaves * 2 - 1) / (kWaves * 2), kThreads, 0, stream>>>(d, e, n, a.grid, a.lam);
   else
     tridiag_eigvals_kernel<64><<<(n + kWaves - 1) / kWaves, kThreads, 0, stream>>>(d, e, n, a.grid, a.lam);
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-}  // namespace tea
-
-// ------------------------------------------------------------------------------------------
-// K9c: diagonal-block Cholesky + triangular inverse for the blocked FP64 Cholesky of FID's
-// covariance (metrics/image/fid.py).  rocSOLVER's potrf at D = 2048 spent ~2.7 ms in 17
-// potf2 launches (~160 us each) and ~1.7 ms in its forward-substitution trsm
-// (profiles/rocprof_k9b_symeig_r2.csv); here one workgroup factors a b x b (b <= 64) diagonal
-// block in registers (potf2, LAPACK semantics: a non-positive pivot records info = column + 1 and
-// stops) and inverts the factor alongside, so the panel below becomes one GEMM with the inverse
-// and the trailing update one GEMM (rocBLAS/hipBLASLt FP64 MFMA) - no trsm, no small-kernel
-// chains.
-namespace tea {
-namespace {
-
-constexpr int kPotrfB = 64;
-// 16 x 16 threads, 4 x 4 entries each (4 waves): ~35 us per 64 x 64 block.  Measured
-// alternatives: 32 x 32 threads with 2 x 2 entries 38 us (the 16-wave barrier costs more than
-// the FMAs it spreads), one wave with 8 x 8 entries 79 us (VALU-bound, spills to AGPRs)
-constexpr int kPG = 16;
-constexpr int kPE = kPotrfB / kPG;
-
-// Register-resident: thread (ti, tj) of a kPG x kPG grid holds L[ti + kPG x][tj + kPG y] and
-// the same entries of X (x, y < kPE) in registers for the whole factorisation, and the column
-// loop is unrolled so the pivot's register slot (j / kPG) is a compile-time index.  Per column
-// ONE barrier: the threads holding column j of L / row j of X put their kPE values into an LDS
-// snapshot (double-buffered, so the next column's writes never race this column's reads),
-// every thread reads the snapshot entries its rows and columns need, and updates its entries
-// in registers (right-looking potf2 on the lower triangle, the same elimination applied to the
-// identity).  Round 2's form kept L and X in LDS and re-read / re-wrote them every column: ~80
-// LDS operations per thread per column, 76 us per 64 x 64 block.
-__global__ __launch_bounds__(kPG * kPG) void potrf_block_kernel(double* A, int64_t lda, int k0, int b,
-                                                          double* Linv, int* info) {
-  __shared__ double s_col[2][kPotrfB];  // column j of L (unscaled), per step parity
-  __shared__ double s_xr[2][kPotrfB];   // row j of X (unscaled)
-  const int t = threadIdx.x;
-  const int ti = t / kPG, tj = t % kPG;
-  double* blk = A + (int64_t)k0 * lda + k0;
-  double L[kPE][kPE], X[kPE][kPE];
-#pragma unroll
-  for (int x = 0; x < kPE; ++x)
-#pragma unroll
-    for (int y = 0; y < kPE; ++y) {
-      const int i = ti + kPG * x, k = tj + kPG * y;
-      L[x][y] = (i < b && k <= i) ? blk[(int64_t)i * lda + k] : 0.0;
-      X[x][y] = (i == k && i < b) ? 1.0 : 0.0;
-    }
-  // fully unrolled (no early exit: a break kept the loop rolled, and the pivot slot then went
-  // through dynamic register indexing - 164 us per block)
-  bool bad = false;
-#pragma clang loop unroll(full)
-  for (int j = 0; j < kPotrfB; ++j) {
-    if (j < b && !bad) {  // block-uniform
-      const int q = j / kPG, c = j % kPG, buf = j & 1;
-      if (tj == c) {
-#pragma unroll
-        for (int x = 0; x < kPE; ++x) s_col[buf][ti + kPG * x] = L[x][q];
-      }
-      if (ti == c) {
-#pragma unroll
-        for (int y = 0; y < kPE; ++y) s_xr[buf][tj + kPG * y] = X[q][y];
-      }
-      __syncthreads();
-      const double d = s_col[buf][j];
-      if (!(d > 0.0)) {  // not positive definite (or NaN): LAPACK info, then stop
-        if (t == 0 && *info == 0) *info = k0 + j + 1;
-        bad = true;
-      } else {
-        // 1/sqrt(d) from the hardware estimate + two Newton steps (a handful of FMAs on the
-        // per-column critical path instead of the IEEE sqrt and division sequences)
-        double rs = __builtin_amdgcn_rsq(d);
-        rs = fma(0.5 * rs, fma(-d * rs, rs, 1.0), rs);
-        rs = fma(0.5 * rs, fma(-d * rs, rs, 1.0), rs);
-        const double sq = d * rs, rd = rs * rs;
-        // masked coefficients instead of per-element selects: rows i <= j and columns k <= j
-        // take zero.  Entries above the diagonal (k > i) take updates too: they are never read
-        // (a column snapshot's rows above its pivot are masked here) and are zeroed on output.
-        // X needs no column mask: row j of X is zero past column j.
-        double ci[kPE], ck[kPE], xr[kPE];
-#pragma unroll
-        for (int x = 0; x < kPE; ++x) ci[x] = ti + kPG * x > j ? s_col[buf][ti + kPG * x] * rd : 0.0;
-#pragma unroll
-        for (int y = 0; y < kPE; ++y) {
-          ck[y] = tj + kPG * y > j ? s_col[buf][tj + kPG * y] : 0.0;
-          xr[y] = s_xr[buf][tj + kPG * y];
-        }
-#pragma unroll
-        for (int x = 0; x < kPE; ++x) {
-#pragma unroll
-          for (int y = 0; y < kPE; ++y) {
-            L[x][y] = fma(-ci[x], ck[y], L[x][y]);
-            X[x][y] = fma(-ci[x], xr[y], X[x][y]);
-          }
-        }
-        // finish column j of L and row j of X (the snapshot the other threads read is unscaled)
-        if (tj == c) {
-#pragma unroll
-          for (int x = 0; x < kPE; ++x) {
-            const int i = ti + kPG * x;
-            L[x][q] = i > j ? L[x][q] * rs : (i == j ? sq : L[x][q]);
-          }
-        }
-        if (ti == c) {
-#pragma unroll
-          for (int y = 0; y < kPE; ++y) X[q][y] = tj + kPG * y <= j ? X[q][y] * rs : X[q][y];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int x = 0; x < kPE; ++x)
-#pragma unroll
-    for (int y = 0; y < kPE; ++y) {
-      const int i = ti + kPG * x, k = tj + kPG * y;
-      if (i < b && k < b) {
-        blk[(int64_t)i * lda + k] = k <= i ? L[x][y] : 0.0;
-        Linv[(int64_t)i * b + k] = bad ? 0.0 : X[x][y];
-      }
-    }
-}
-
-}  // namespace
-
-int potrf_block_size() { return kPotrfB; }
-
-int launch_potrf_block(double* A, int64_t lda, int k0, int b, double* Linv, int* info,
-                       hipStream_t stream) {
-  if (b < 1 || b > kPotrfB) return 1;
-  potrf_block_kernel<<<1, kPG * kPG, 0, stream>>>(A, lda, k0, b, Linv, info);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -1,9 +1,7 @@
-"""K3a splitter-bucket mode (csrc/kernels/radix.hip: a sorted 8192-key sample gives 255
-splitters, ONE stable onesweep pass scatters the keys into 256 buckets, one workgroup per bucket
-sorts it in LDS) against torch.sort(stable=True): continuous and clustered scores, tie-heavy rows
-whose tie group exceeds a bucket's LDS capacity, NaN / +-0 / +-inf, payloads, ascending order,
-and a row whose strided sample misrepresents it (buckets past the LDS capacity: the
-single-workgroup LSD path)."""
+"""K3a radix sort (csrc/kernels/radix.hip) on its hardest inputs, against
+torch.sort(stable=True): continuous and clustered scores, a 40% tie group, seven-level scores,
+NaN / +-0 / +-inf, scores crowded under 1.0, a constant row, a row whose strided sample is all one
+value, payloads of every dtype, ascending order, and several rows - at 64k to 2M keys a row."""
 
 import pytest
 import torch
@@ -12,19 +10,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-@pytest.fixture(autouse=True)
-def _bucket_mode(monkeypatch):
-    # opt-in mode (read per sort): measured slower than the default onesweep passes at 1M
-    monkeypatch.setenv("TORCHEVAL_AMD_K3_BUCKET", "1")
-
-
 def _check(x: torch.Tensor, payload=None, kind: int = 0, ascending: bool = False) -> None:
     from torcheval_amd.ops import native
 
     xd = x.to(DEV)
     s = torch.empty_like(xd)
     idx = torch.empty(xd.shape, dtype=torch.int32, device=DEV)
-    native().sort_desc(xd, s, idx, None if payload is None else payload.to(DEV), kind, None, ascending)
+    native().sort_desc(xd, s, idx, None if payload is None else payload.to(DEV), kind, ascending)
     ref_vals, ref_idx = torch.sort(x, dim=-1, descending=not ascending, stable=True)
     torch.testing.assert_close(s.cpu(), ref_vals, equal_nan=True, rtol=0, atol=0)
     got = idx.cpu().long()
@@ -46,7 +38,7 @@ def _gen(kind: str, n: int, seed: int) -> torch.Tensor:
         return torch.randn(1, n, generator=g) * 3
     if kind == "sigmoid_confident":  # most scores crowd just below 1.0
         return torch.sigmoid(torch.randn(1, n, generator=g) * 3 + 6)
-    if kind == "ties40":  # a 40% tie group: one bucket over the LDS capacity, tie run appended
+    if kind == "ties40":  # a 40% tie group: one digit run spanning hundreds of tiles
         x = torch.rand(1, n, generator=g)
         x[:, torch.rand(n, generator=g) < 0.4] = 0.5
         return x
@@ -68,7 +60,7 @@ def _gen(kind: str, n: int, seed: int) -> torch.Tensor:
 
 @pytest.mark.parametrize("kind", ["uniform", "logits", "sigmoid_confident", "ties40", "levels", "special", "constant"])
 @pytest.mark.parametrize("n", [65536, 1_000_000, 2_000_000])
-def test_bucket_sort_matches_stable_sort(kind, n):
+def test_sort_matches_stable_sort(kind, n):
     _check(_gen(kind, n, n + len(kind)))
 
 
@@ -94,9 +86,8 @@ def test_multi_row():
     _check(x)
 
 
-def test_misleading_sample_takes_the_lsd_path():
-    # every strided sample position (i * n / 8192) holds 0.5: all splitters equal, so two buckets
-    # of ~n / 2 distinct keys each exceed the LDS capacity
+def test_constant_strided_sample():
+    # every strided sample position (i * n / 8192) holds 0.5 among otherwise distinct keys
     n = 1 << 20
     g = torch.Generator().manual_seed(9)
     x = torch.rand(1, n, generator=g)
@@ -107,7 +98,7 @@ def test_misleading_sample_takes_the_lsd_path():
     _check(x, t, 1)
 
 
-def test_binary_auroc_matches_cpu_on_bucket_path():
+def test_binary_auroc_matches_cpu_on_hard_inputs():
     from torcheval_amd.metrics.functional import binary_auprc, binary_auroc
 
     g = torch.Generator().manual_seed(11)

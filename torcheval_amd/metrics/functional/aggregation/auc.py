@@ -32,7 +32,7 @@ def _auc_native(x: torch.Tensor, y: torch.Tensor) -> Optional[torch.Tensor]:
     xs = x.contiguous()
     s = torch.empty(xs.shape, dtype=torch.float32, device=x.device)
     order = torch.empty(xs.shape, dtype=torch.int32, device=x.device)
-    native().sort_desc(xs, s, order, y.contiguous(), PAYLOAD_TARGET, None, True)  # ascending, stable
+    native().sort_desc(xs, s, order, y.contiguous(), PAYLOAD_TARGET, True)  # ascending, stable
     out = torch.empty(xs.shape[0], dtype=torch.float32, device=x.device)
     native().trapz_sorted(s, order, out)
     return out
