@@ -8,8 +8,11 @@
 // wave ballots, and the per-block row count goes through the sharded fold (tea_fold.h) into
 // the float32 ``num_correct`` state; block 0 also adds the update's total.  Top-k keeps the
 // row in registers (R values per lane, C <= 64 R) and selects k maxima with packed
-// (order-preserving key, ~index) u64 wave reductions - ties resolve to the lowest index and
-// NaN ranks highest, as in torch.topk.
+// (order-preserving key, ~index) u64 wave reductions.  The ranking is this project's own rule
+// (docs/parity.md): by value with -0.0 == +0.0; every NaN, of any sign or payload, ranks above
+// +inf and all NaNs are equal; among equal scores the lowest column index wins - the first k
+// indices of a stable descending sort.  torch.topk's choice among ties at rank k is
+// implementation-defined and is not followed.
 #include "tea_common.h"
 #include "tea_fold.h"
 #include "tea_kernels.h"
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(kB) void ml_threshold_kernel(MultilabelArgs a) {
 __device__ __forceinline__ uint32_t order_key(float v) {
   uint32_t u = __float_as_uint(v);
   if (v != v) u = 0x7fc00000u;  // canonical NaN: above +inf after the flip
+  if (v == 0.f) u = 0u;         // -0.0 == +0.0: one key for both zeros
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
