@@ -232,6 +232,15 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.structural_similarity(x, t)
         return make
 
+    def ndcg(cls):
+        def make():
+            x, t = rand(B, C), randint(5, B, C)
+            if cls:
+                m = M.NormalizedDCG(k=10, device=dev)
+                return lambda: m.update(x, t)
+            return lambda: F.normalized_dcg(x, t, k=10)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -374,6 +383,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "topk_multilabel_accuracy 8192x1000": topk_ml,
         "reciprocal_rank 8192x1000 k=10 (K10)": rr,
         "HitRate(k=10).update 8192x1000 (K10)": hr,
+        "normalized_dcg 8192x1000 k=10 (K13)": ndcg(False),
+        "NormalizedDCG(k=10).update 8192x1000 (K13)": ndcg(True),
         "perplexity (4,1024,32000)": ppl,
         "mean_squared_error 8192x1000": mse,
         "r2_score 8192x1000": r2,

@@ -1348,6 +1348,86 @@ void ssim(const Tensor& input, const Tensor& target, const std::vector<double>& 
   check_launch(tea::launch_ssim(a, stream), "ssim");
 }
 
+// K13: normalized DCG per row (csrc/kernels/ndcg.hip).  ``out`` takes the [n] float32 row values;
+// the optional class states take += sum of the (unrounded) values and += n; ``err`` gets bit 0
+// when a relevance is negative or NaN.
+//
+// The discount prefix table D[0] = 0, D[m] = sum_{r < m} 1 / log2(r + 2) does not depend on the
+// cutoff, so one table of kNdcgMaxColumns + 1 doubles per device serves every call: summed
+// sequentially in FP64 on the host, copied once.  Warm it up before any HIP-graph capture.
+const double* ndcg_discounts(const Tensor& like) {
+  static std::mutex mu;
+  // process-lifetime (never destroyed), as the workspaces above
+  static auto& cache = *new std::unordered_map<int, Tensor>();
+  std::lock_guard<std::mutex> lock(mu);
+  const int dev = like.device().index();
+  auto it = cache.find(dev);
+  if (it == cache.end()) {
+    Tensor host = at::empty({tea::kNdcgMaxColumns + 1}, at::TensorOptions().dtype(at::kDouble));
+    double* d = host.data_ptr<double>();
+    d[0] = 0.0;
+    for (int r = 0; r < tea::kNdcgMaxColumns; ++r) d[r + 1] = d[r] + 1.0 / std::log2(static_cast<double>(r) + 2.0);
+    it = cache.emplace(dev, host.to(like.device())).first;
+  }
+  return it->second.data_ptr<double>();
+}
+
+void ndcg(const Tensor& input, const Tensor& target, int64_t k, bool exponential_gain,
+          const optional<Tensor>& out, const optional<Tensor>& ndcg_sum, const optional<Tensor>& num_rows,
+          const optional<Tensor>& err) {
+  check_gpu(input, "input");
+  check_gpu(target, "target");
+  TORCH_CHECK(input.dim() == 2 && target.sizes() == input.sizes() && target.device() == input.device(),
+              "ndcg: input and target must be [n, c] tensors of one shape on one device");
+  const int64_t n = input.size(0), c = input.size(1);
+  TORCH_CHECK(c >= 1 && c <= tea::kNdcgMaxColumns, "ndcg: 1 .. ", tea::kNdcgMaxColumns, " columns, got ", c);
+  TORCH_CHECK(k >= 1 && k <= c, "ndcg: the cutoff must lie in 1 .. c, got ", k);
+  TORCH_CHECK((c == 1 || (input.stride(1) == 1 && target.stride(1) == 1)) && input.stride(0) >= 0 &&
+                  target.stride(0) >= 0,
+              "ndcg: input and target need a unit column stride");
+  const auto xt = input.scalar_type(), tt = target.scalar_type();
+  TORCH_CHECK(xt == at::kFloat || xt == at::kHalf || xt == at::kBFloat16,
+              "ndcg: scores must be float32, float16 or bfloat16");
+  TORCH_CHECK(tt == at::kFloat || tt == at::kHalf || tt == at::kBFloat16 || tt == at::kLong || tt == at::kInt ||
+                  tt == at::kShort || tt == at::kChar || tt == at::kByte,
+              "ndcg: unsupported relevance dtype ", tt);
+  TORCH_CHECK(out.has_value() || ndcg_sum.has_value(), "ndcg: nothing to write");
+  TORCH_CHECK(ndcg_sum.has_value() == num_rows.has_value(), "ndcg: pass both class states or neither");
+  if (n == 0) return;
+  tea::NdcgArgs a;
+  a.x = input.data_ptr();
+  a.x_dt = dt_of(input);
+  a.x_stride = input.stride(0);
+  a.t = target.data_ptr();
+  a.t_dt = dt_of(target);
+  a.t_stride = target.stride(0);
+  a.n = n;
+  a.c = static_cast<int>(c);
+  a.k = static_cast<int>(k);
+  a.exponential = exponential_gain ? 1 : 0;
+  a.out = f32_out(out, input, n, "out");
+  for (const auto* s : {&ndcg_sum, &num_rows}) {
+    if (!s->has_value()) continue;
+    const Tensor& t = **s;
+    TORCH_CHECK(t.scalar_type() == at::kDouble && t.numel() == 1 && t.device() == input.device(),
+                "ndcg: class states must be float64 scalars on the inputs' device");
+  }
+  if (err.has_value()) {
+    TORCH_CHECK(err->scalar_type() == at::kInt && err->numel() >= 1 && err->device() == input.device(),
+                "ndcg: err must be an int32 tensor on the input device");
+    a.err = err->data_ptr<int>();
+  }
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  const hipStream_t stream = stream_for(input);
+  a.D = ndcg_discounts(input);
+  if (ndcg_sum.has_value()) {
+    a.ndcg_sum = ndcg_sum->data_ptr<double>();
+    a.num_rows = num_rows->data_ptr<double>();
+    a.partial = static_cast<double*>(scratch_workspace(input, stream, tea::ndcg_blocks(n, c) * 8, 15));
+  }
+  check_launch(tea::launch_ndcg(a, stream), "ndcg");
+}
+
 // FID compute glue (csrc/kernels/fid_prep.hip): FP64 symmetric covariance from the FP32 states.
 void cov_finalize(const Tensor& cov_sum, const Tensor& colsum, double n, const Tensor& out) {
   check_gpu(cov_sum, "cov_sum");
@@ -1877,6 +1957,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ssim_tile_cols", [] { return tea::kSsimTileW; }, "K12 output tile columns");
   m.def("ssim_max_kernel_size", [] { return tea::kSsimMaxKs; }, "K12 largest native window");
   m.def("ssim_geometry_ok", &tea::ssim_geometry_ok, "K12 launchable (planes, h, w, kernel_size)");
+  m.def("ndcg", &ndcg, "K13 normalized DCG per row: float32 row values, optional class states and error flag",
+        py::arg("input"), py::arg("target"), py::arg("k"), py::arg("exponential_gain"),
+        py::arg("out"), py::arg("ndcg_sum") = py::none(), py::arg("num_rows") = py::none(),
+        py::arg("err") = py::none());
+  m.def("ndcg_max_columns", [] { return tea::kNdcgMaxColumns; }, "K13 largest native row width");
   m.def("cov_finalize", &cov_finalize, "FP64 symmetric covariance from FP32 FID states",
         py::arg("cov_sum"), py::arg("colsum"), py::arg("n"), py::arg("out"));
   m.def("sym_fill_upper", &sym_fill_upper, "mirror the lower triangle of a float64 matrix into its upper",
@@ -2035,6 +2120,8 @@ TORCH_LIBRARY(torcheval_amd, m) {
   m.def("trapz_sorted(Tensor x, Tensor y_bits, Tensor(a!) out) -> ()");
   m.def("ssim(Tensor input, Tensor target, float[] taps, float c1, float c2, Tensor(a!)? out, bool mean, "
         "Tensor(b!)? mssim_sum, Tensor(c!)? num_images) -> ()");
+  m.def("ndcg(Tensor input, Tensor target, int k, bool exponential_gain, Tensor(a!)? out, "
+        "Tensor(b!)? ndcg_sum, Tensor(c!)? num_rows, Tensor(d!)? err) -> ()");
   m.def("seg_reduce_rows(Tensor rows, Tensor(a!) out, int ws, int[] offs, int[] counts, int[] dtypes, "
         "int[] ops) -> ()");
   m.def("row_sums(Tensor x, Tensor? t, Tensor? w, float w_scalar, Tensor(a!)[] outs, int[] codes, int rows) -> ()");
@@ -2073,6 +2160,7 @@ TORCH_LIBRARY_IMPL(torcheval_amd, CUDA, m) {
   m.impl("fid_finish", &fid_finish);
   m.impl("trapz_sorted", &trapz_sorted);
   m.impl("ssim", &op_ssim);
+  m.impl("ndcg", &ndcg);
   m.impl("seg_reduce_rows", &op_seg_reduce_rows);
   m.impl("row_sums", &op_row_sums);
   m.impl("sort_desc", &op_sort_desc);
@@ -2121,6 +2209,8 @@ TORCH_LIBRARY_IMPL(torcheval_amd, Meta, m) {
   m.impl("trapz_sorted", [](const Tensor&, const Tensor&, const Tensor&) {});
   m.impl("ssim", [](const Tensor&, const Tensor&, at::ArrayRef<double>, double, double, const optional<Tensor>&, bool,
                     const optional<Tensor>&, const optional<Tensor>&) {});
+  m.impl("ndcg", [](const Tensor&, const Tensor&, int64_t, bool, const optional<Tensor>&,
+                    const optional<Tensor>&, const optional<Tensor>&, const optional<Tensor>&) {});
   m.impl("seg_reduce_rows", [](const Tensor&, const Tensor&, int64_t, at::IntArrayRef, at::IntArrayRef,
                                at::IntArrayRef, at::IntArrayRef) {});
   m.impl("cls_counts", [](const Tensor&, const Tensor&, int64_t, int64_t, const optional<Tensor>&,

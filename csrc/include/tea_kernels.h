@@ -625,3 +625,30 @@ int64_t ssim_tiles(int64_t h, int64_t w, int64_t ks);  // output tiles per plane
 bool ssim_geometry_ok(int64_t planes, int64_t h, int64_t w, int64_t ks);
 int launch_ssim(const SsimArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K13: normalized discounted cumulative gain per row of [n, c] scores / graded relevance
+// (csrc/kernels/ndcg.hip).  c <= 64 runs a wave per row, larger c a workgroup per row with the
+// row sorted in LDS; kNdcgMaxColumns keeps two such workgroups on a CU (2 * 4096 * 8 B each).
+constexpr int kNdcgMaxColumns = 4096;
+struct NdcgArgs {
+  const void* x = nullptr;  // [n, c] scores, unit column stride: f32 / f16 / bf16
+  DType x_dt = DType::f32;
+  int64_t x_stride = 0;     // elements between rows
+  const void* t = nullptr;  // [n, c] relevance, unit column stride: f32 / f16 / bf16 / i64 / i32 / i16 / i8 / u8
+  DType t_dt = DType::i64;
+  int64_t t_stride = 0;
+  int64_t n = 0;
+  int c = 0;                // 1 .. kNdcgMaxColumns
+  int k = 0;                // cutoff, 1 .. c
+  int exponential = 0;      // gain 2^t - 1 instead of t
+  const double* D = nullptr;  // [k + 1] prefix sums of 1 / log2(r + 2), D[0] = 0
+  float* out = nullptr;       // [n] row values; may be null when the class states are given
+  double* partial = nullptr;  // [ndcg_blocks(n, c)] scratch, with the class states
+  double* ndcg_sum = nullptr;   // class states (both or neither): += sum of the row values, += n
+  double* num_rows = nullptr;
+  int* err = nullptr;           // bit 0: a relevance with !(t >= 0) (row scored NaN)
+};
+int ndcg_blocks(int64_t n, int64_t c);  // grid of the row launch = number of partials
+int launch_ndcg(const NdcgArgs& a, hipStream_t stream);
+}  // namespace tea

@@ -14,6 +14,7 @@ from torcheval_amd.metrics.functional.ranking.click_through_rate import (
 )
 from torcheval_amd.metrics.functional.ranking.frequency import frequency_at_k
 from torcheval_amd.metrics.functional.ranking.hit_rate import hit_rate
+from torcheval_amd.metrics.functional.ranking.ndcg import normalized_dcg
 from torcheval_amd.metrics.functional.ranking.reciprocal_rank import reciprocal_rank
 from torcheval_amd.metrics.functional.ranking.num_collisions import num_collisions
 from torcheval_amd.metrics.functional.ranking.weighted_calibration import (
@@ -34,6 +35,7 @@ __all__ = [
     "click_through_rate",
     "frequency_at_k",
     "hit_rate",
+    "normalized_dcg",
     "num_collisions",
     "reciprocal_rank",
     "retrieval_precision",

@@ -3,6 +3,7 @@
 from torcheval_amd.metrics.ranking._score_list import _ScoreList, _RankScoreList
 from torcheval_amd.metrics.ranking.click_through_rate import ClickThroughRate
 from torcheval_amd.metrics.ranking.hit_rate import HitRate
+from torcheval_amd.metrics.ranking.ndcg import NormalizedDCG
 from torcheval_amd.metrics.ranking.reciprocal_rank import ReciprocalRank
 from torcheval_amd.metrics.ranking.retrieval_precision import RetrievalPrecision
 from torcheval_amd.metrics.ranking.weighted_calibration import WeightedCalibration
@@ -10,6 +11,7 @@ from torcheval_amd.metrics.ranking.weighted_calibration import WeightedCalibrati
 __all__ = [
     "ClickThroughRate",
     "HitRate",
+    "NormalizedDCG",
     "ReciprocalRank",
     "RetrievalPrecision",
     "WeightedCalibration",
