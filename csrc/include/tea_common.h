@@ -3,7 +3,7 @@
 // Conventions
 //  * wave64 everywhere: lane = threadIdx.x & 63, reductions over 64 lanes.
 //  * loads are 16 B per lane (Guideline 13): float4 for f32, 8 x 16-bit for bf16/f16.
-//  * kernels take raw pointers + a DType tag; the pybind layer (csrc/bindings.cpp) owns the
+//  * kernels take raw pointers + a DType tag; the pybind layer (csrc/bindings/) owns the
 //    torch::Tensor plumbing so kernel TUs compile in seconds (no torch headers here).
 #pragma once
 

@@ -8,7 +8,7 @@
 // first-index tie rule, or the rank-of-target test for k > 1) and a single 0-d output.
 #include <ATen/ATen.h>
 #include <pybind11/pybind11.h>
-#include <torch/extension.h>
+#include <torch/csrc/utils/pybind.h>
 
 #include <algorithm>
 #include <cfloat>
@@ -144,7 +144,7 @@ float* opt_f32(const c10::optional<at::Tensor>& t, int64_t numel, const char* na
   return t->data_ptr<float>();
 }
 
-// Same arguments and semantics as the HIP ``cls_counts`` (csrc/bindings.cpp): per row the
+// Same arguments and semantics as the HIP ``cls_counts`` (csrc/bindings/counts.cpp): per row the
 // prediction (argmax of [N, C] scores or the [N] label) or, for k > 1, the rank-of-target
 // test; then micro counts and the class histograms, accumulated in float32.  Rows with an
 // out-of-range label are skipped and flagged in ``err`` as on the GPU (callers validate first

@@ -11,7 +11,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
-#include <torch/extension.h>
+#include <torch/csrc/utils/pybind.h>
 
 #include <atomic>
 #include <cstring>

@@ -35,7 +35,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 #include <rccl/rccl.h>
-#include <torch/extension.h>
+#include <torch/csrc/utils/pybind.h>
 #include <torch/library.h>
 
 #include <algorithm>
@@ -628,6 +628,7 @@ void tea_register_rccl(pybind11::module_& m) {
 }
 
 TORCH_LIBRARY_FRAGMENT(torcheval_amd, m) {
+  // no Meta kernels: collectives over a live communicator handle, which no traced graph can hold
   m.def("rccl_all_gather(int handle, Tensor src, Tensor(a!) dst) -> ()");
   m.def("rccl_all_reduce(int handle, Tensor(a!) t, int op, Tensor(b!)? out=None) -> ()");
 }

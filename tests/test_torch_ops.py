@@ -1,5 +1,6 @@
 """The native kernels are registered with the torch dispatcher (torch.ops.torcheval_amd.*):
-CPU (host twin) and Meta kernels here; the CUDA kernels in tests/gpu/test_torch_ops_gpu.py."""
+the CPU host twin and Meta kernels here; the CUDA kernels in tests/gpu/test_torch_ops_gpu.py.
+26 of the 32 ops have a Meta kernel; tests/test_native_api.py lists which and calls each."""
 
 import pytest
 import torch
