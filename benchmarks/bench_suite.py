@@ -241,6 +241,15 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.normalized_dcg(x, t, k=10)
         return make
 
+    def spearman(cls):
+        def make():
+            x, y = rand(N1M), rand(N1M)
+            if cls:
+                m = M.SpearmanCorrCoef(device=dev).update(x, y)
+                return lambda: m.compute()
+            return lambda: F.spearman_corrcoef(x, y)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -388,6 +397,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "perplexity (4,1024,32000)": ppl,
         "mean_squared_error 8192x1000": mse,
         "r2_score 8192x1000": r2,
+        "spearman_corrcoef N=1M (K3a + K14)": spearman(False),
+        "SpearmanCorrCoef.compute N=1M (K3a + K14)": spearman(True),
         "Sum.update 8192x1000 (K5b)": k5b(M.Sum, "sum"),
         "Mean.update 8192x1000 (K5b)": k5b(M.Mean, "sum"),
         "PeakSignalNoiseRatio.update 8192x1000 (K5b)": k5b(M.PeakSignalNoiseRatio, "psnr"),

@@ -1,5 +1,5 @@
 // torcheval_amd._C bindings (layout: module.cpp): K3a radix sort (with the onesweep fault handling), K3 scan,
-// K3c curves, K3t trapezoids, the f32 transpose.
+// K3c curves, K3t trapezoids, the f32 transpose, K14 rank correlation.
 #include <ATen/ATen.h>
 #include <torch/csrc/utils/pybind.h>
 #include <torch/library.h>
@@ -391,6 +391,42 @@ void trapz_sorted(const Tensor& x, const Tensor& y_bits, const Tensor& out) {
                "trapz_sorted");
 }
 
+// K14: Spearman's rho per row from one K3a sort of both operands (csrc/kernels/rankcorr.hip):
+// sorted f32 and order int32, contiguous [2 rows, n] (the first operand's rows, then the
+// second's); out f32 [rows]
+void rank_corr(const Tensor& sorted, const Tensor& order, const Tensor& out) {
+  check_gpu(sorted, "sorted");
+  TORCH_CHECK(sorted.dim() == 2 && sorted.scalar_type() == at::kFloat && sorted.is_contiguous() &&
+                  sorted.size(0) % 2 == 0,
+              "rank_corr: sorted must be contiguous float32 [2 rows, n]");
+  TORCH_CHECK(order.scalar_type() == at::kInt && order.is_contiguous() && order.sizes() == sorted.sizes() &&
+                  order.device() == sorted.device(),
+              "rank_corr: order must be contiguous int32 [2 rows, n]");
+  const int64_t rows = sorted.size(0) / 2, n = sorted.size(1);
+  TORCH_CHECK(n >= 2 && n < (int64_t{1} << 31), "rank_corr: rows of 2 .. 2^31 - 1 samples, got ", n);
+  f32_out(out, sorted, rows, "out");
+  if (rows == 0) return;
+  DeviceGuard guard(sorted.device());
+  const hipStream_t st = stream_for(sorted);
+  tea::RankCorrArgs a;
+  a.sorted = sorted.data_ptr<float>();
+  a.order = order.data_ptr<int32_t>();
+  a.rows = rows;
+  a.n = n;
+  a.pitch = tea::rank_corr_pitch(n);
+  Tensor ws = at::empty({2 * rows * a.pitch + 2 * rows}, sorted.options().dtype(at::kInt));
+  a.c = ws.data_ptr<int32_t>();
+  a.nan_flag = a.c + 2 * rows * a.pitch;
+  a.part = static_cast<double*>(
+      scratch_workspace(sorted, st, rows * tea::rank_moments_blocks(n) * 3 * 8, Scratch::kRankCorrPartials));
+  // the timeout word of the onesweep sort that produced `sorted`.  More than 8 stacked rows took
+  // the legacy passes, which neither set nor clear that word: an older sort's flag is not theirs
+  if (tea::radix_onesweep_ok(2 * rows, n))
+    a.sort_fault = static_cast<const uint32_t*>(zeroed_workspace(sorted, st, 16 * 4, Zeroed::kOnesweepHeader)) + 8;
+  a.out = out.data_ptr<float>();
+  check_launch(tea::launch_rank_corr(a, st), "rank_corr");
+}
+
 }  // namespace
 
 void tea_bind_sortscan(py::module_& m) {
@@ -452,4 +488,21 @@ TORCH_LIBRARY_IMPL(torcheval_amd, Meta, m) {
   m.impl("rafp", &MetaNoop<&rafp>::call);
   m.impl("trapz_sorted", &MetaNoop<&trapz_sorted>::call);
   m.impl("transpose_f32", &MetaNoop<&transpose_f32>::call);
+}
+
+// K14's op: schema, CUDA kernel, Meta kernel.  It sits in a dispatcher namespace of its own and
+// has no pybind entry, because the attributes of `_C` and the `torcheval_amd::` ops are recorded
+// in tests/golden/native_api.json and that fixture stays byte for byte what it was.  Eager and
+// compiled calls both take the dispatcher (ops/rankcorr.py);
+// tests/metrics/regression/test_spearman.py pins the schema, the dispatch keys and the Meta kernel.
+TORCH_LIBRARY(torcheval_amd_rankcorr, m) {
+  m.def("rank_corr(Tensor sorted, Tensor order, Tensor(a!) out) -> ()");
+}
+
+TORCH_LIBRARY_IMPL(torcheval_amd_rankcorr, CUDA, m) {
+  m.impl("rank_corr", &rank_corr);
+}
+
+TORCH_LIBRARY_IMPL(torcheval_amd_rankcorr, Meta, m) {
+  m.impl("rank_corr", &MetaNoop<&rank_corr>::call);
 }

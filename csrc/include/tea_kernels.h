@@ -652,3 +652,26 @@ struct NdcgArgs {
 int ndcg_blocks(int64_t n, int64_t c);  // grid of the row launch = number of partials
 int launch_ndcg(const NdcgArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K14: Spearman rank correlation per row (csrc/kernels/rankcorr.hip) of two operands that K3a has
+// sorted as one [2 rows, n] stack, the first operand's rows and then the second's (descending
+// sorted rows and their int32 source permutations, payload_kind 0).
+constexpr int kRankCenterSpan = 2048;   // sorted positions a rank_center block resolves in LDS
+constexpr int kRankMomentsSpan = 4096;  // elements per round of a rank_moments block; its span is a multiple
+struct RankCorrArgs {
+  const float* sorted = nullptr;   // [2 rows, n] sorted keys, contiguous
+  const int32_t* order = nullptr;  // [2 rows, n] source index of each sorted position
+  int64_t rows = 0;
+  int64_t n = 0;                // 2 .. 2^31 - 1
+  int32_t* c = nullptr;         // [2, rows, pitch] centred doubled ranks in source order, 16-byte aligned
+  int64_t pitch = 0;            // rank_corr_pitch(n)
+  int32_t* nan_flag = nullptr;  // [2, rows]: the operand's row holds a NaN
+  double* part = nullptr;       // [rows, rank_moments_blocks(n), 3] scratch: sxy, sxx, syy
+  const uint32_t* sort_fault = nullptr;  // K3a's onesweep timeout word or null (non-zero: every row scores NaN)
+  float* out = nullptr;         // [rows]
+};
+int64_t rank_corr_pitch(int64_t n);
+int rank_moments_blocks(int64_t n);
+int launch_rank_corr(const RankCorrArgs& a, hipStream_t stream);
+}  // namespace tea

@@ -104,9 +104,10 @@ enum class Zeroed : int {
   kRetrievalCounts = 7,     // K10b
   kMomentsTickets = 8,      // K5 v2
   kRowSumsTickets = 9,      // K5b
-  // the onesweep header, whose word 8 is the look-back timeout flag.  Shared on purpose by three
-  // users that must see the same buffer: sort_desc writes it, auc_scan reads the flag on the
-  // device (AucScanArgs::sort_fault) and sort_desc_timeouts reads / clears it from the host
+  // the onesweep header, whose word 8 is the look-back timeout flag.  Shared on purpose by four
+  // users that must see the same buffer: sort_desc writes it, auc_scan and rank_corr read the
+  // flag on the device (AucScanArgs / RankCorrArgs::sort_fault) and sort_desc_timeouts reads /
+  // clears it from the host
   kOnesweepHeader = 10,
   kOnesweepStatus = 11,     // K3a
   kOnesweepGroups = 12,     // K3a
@@ -122,6 +123,7 @@ enum class Scratch : int {
   kTrapzPartials = 13,      // K3t
   kSsimPartials = 14,       // K12
   kNdcgPartials = 15,       // K13
+  kRankCorrPartials = 16,   // K14
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

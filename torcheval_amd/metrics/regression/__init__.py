@@ -2,9 +2,11 @@
 
 from torcheval_amd.metrics.regression.mean_squared_error import MeanSquaredError
 from torcheval_amd.metrics.regression.r2_score import R2Score
+from torcheval_amd.metrics.regression.spearman import SpearmanCorrCoef
 
 __all__ = [
     "MeanSquaredError",
     "R2Score",
+    "SpearmanCorrCoef",
 ]
 __doc_name__ = "Regression Metrics"
