@@ -6,9 +6,11 @@
 // once with 16-B loads, keeping a per-lane online (max, sum-exp) pair that is rescaled once per
 // 16-value chunk; lanes combine their pairs with xor shuffles; lane 0 adds
 //   -log p(target) = logsumexp(row) - row[target]
-// in FP64.  Rows that do not start 16-B aligned (odd vocabularies) stream a scalar head, a 16-B
-// body and a scalar tail.  ``ignore_index`` rows are skipped and counted out; targets outside [0, V) are
-// flagged on device (``err``) instead of the reference's host-synchronising max() check.
+// in FP64.  -inf logits count as masked (probability 0); a NaN or +inf logit in a counted row makes
+// the result NaN; ignored rows are never read.  Rows that do not start 16-B aligned (odd
+// vocabularies) stream a scalar head, a 16-B body and a scalar tail.  ``ignore_index`` rows are
+// skipped and counted out; targets outside [0, V) are flagged on device (``err``) instead of the
+// reference's host-synchronising max() check.
 #include "tea_common.h"
 #include "tea_kernels.h"
 
@@ -58,10 +60,35 @@ __device__ __forceinline__ float load1(const void* row, int64_t col) {
   return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
 }
 
+// -inf logits are masked entries (probability 0); a NaN or +inf logit makes the row's sum NaN.
+// Where a maximum is still -inf, the exponent is taken against 0 instead: exp(-inf - 0) = 0 where
+// exp(-inf - -inf) would be NaN, and a NaN value or sum still reaches s.
+__device__ __forceinline__ float finite_or_zero(float mx) { return mx == -__builtin_huge_valf() ? 0.f : mx; }
+
 __device__ __forceinline__ void combine(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
-  if (mn == -__builtin_huge_valf()) return;  // both empty
-  s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
+  const float ms = finite_or_zero(mn);  // both empty: s = 0, or NaN when either side brings one
+  s = s * __expf(m - ms) + s2 * __expf(m2 - ms);
+  m = mn;
+}
+
+// Fold H * 8 loaded values into the lane's (m, s): the new maximum first, then every exponent
+// against it, so that one step costs one select and one rescale.
+template <int H>
+__device__ __forceinline__ void absorb(const float (&v)[H][8], float& m, float& s) {
+  float cm = v[0][0];
+#pragma unroll
+  for (int h = 0; h < H; ++h)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cm = fmaxf(cm, v[h][e]);
+  const float mn = fmaxf(m, cm);
+  const float ms = finite_or_zero(mn);  // all -inf so far: the step adds 0, or NaN if it holds one
+  float cs = 0.f;
+#pragma unroll
+  for (int h = 0; h < H; ++h)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cs += __expf(v[h][e] - ms);
+  s = s * __expf(m - ms) + cs;
   m = mn;
 }
 
@@ -76,17 +103,7 @@ __device__ __forceinline__ void chunk16(const void* p, int64_t base, int64_t n, 
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[1][e] = -__builtin_huge_valf();
   }
-  float cm = v[0][0];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cm = fmaxf(cm, v[h][e]);
-  float cs = 0.f;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cs += __expf(v[h][e] - cm);
-  combine(m, s, cm, cs);
+  absorb<2>(v, m, s);
 }
 
 // Stream n values (n % 16 == 0, p 16-B aligned) as 16-value chunks per lane.  U2: two chunks a
@@ -103,17 +120,7 @@ __device__ __forceinline__ void stream_row(const void* p, int64_t n, int lane, f
       load8<KIND>(p, base + 8, v[1]);
       load8<KIND>(p, base + step, v[2]);
       load8<KIND>(p, base + step + 8, v[3]);
-      float cm = v[0][0];
-#pragma unroll
-      for (int h = 0; h < 4; ++h)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) cm = fmaxf(cm, v[h][e]);
-      float cs = 0.f;
-#pragma unroll
-      for (int h = 0; h < 4; ++h)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) cs += __expf(v[h][e] - cm);
-      combine(m, s, cm, cs);
+      absorb<4>(v, m, s);
     }
   }
   for (; base < n; base += step) chunk16<KIND>(p, base, n, m, s);
@@ -147,18 +154,18 @@ __global__ __launch_bounds__(kB) void perplexity_kernel(PerplexityArgs a) {
       const int64_t c = head + nb + lane;
       if (c < a.v) combine(m, s, load1<KIND>(rp, c), 1.f);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, kWave);
-      const float s2 = __shfl_xor(s, o, kWave);
-      combine(m, s, m2, s2);
-    }
+    // the row maximum first (a lane's m is never NaN), then one rescale per lane and a plain sum:
+    // an empty lane adds 0, a NaN in any lane's s reaches the row's
+    const float mw = wave_max(m);
+    s = wave_sum(s * __expf(m - finite_or_zero(mw)));
+    m = mw;
     if (lane == 0) {
       if (t < 0 || t >= a.v) {
         if (a.err) atomicOr(a.err, 1);
       } else {
-        const double lse = static_cast<double>(m) + log(static_cast<double>(s));
-        acc += lse - static_cast<double>(load1<KIND>(rp, t));
+        // (m - x[t]) first: at |m| near the top of the float range m + log(s) would lose log(s)
+        const double gap = static_cast<double>(m) - static_cast<double>(load1<KIND>(rp, t));
+        acc += gap + log(static_cast<double>(s));
         cnt += 1.0;
       }
     }

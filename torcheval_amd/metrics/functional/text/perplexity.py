@@ -23,7 +23,7 @@ def perplexity(input: torch.Tensor, target: torch.Tensor, ignore_index: Optional
         sum_log_probs, num_total = _perplexity_update(input, target, ignore_index, err=flag)
         out = _perplexity_compute(sum_log_probs, num_total)
         if read_int(flag) != 0:
-            _perplexity_label_check(input, target, ignore_index)
+            _perplexity_flag_raise(input, target, ignore_index)
         return out
     sum_log_probs, num_total = _perplexity_update(input, target, ignore_index)
     return _perplexity_compute(sum_log_probs, num_total)
@@ -50,7 +50,7 @@ def _perplexity_update(
 
         native().perplexity_sums(logits, tgt, ignore_index, out, flag, config.deterministic)
         if err is None and read_int(flag) != 0:
-            _perplexity_label_check(input, target, ignore_index)
+            _perplexity_flag_raise(input, target, ignore_index)
         return out[0], out[1]
     _perplexity_label_check(input, target, ignore_index)
     if ignore_index is not None:
@@ -89,6 +89,16 @@ def _perplexity_label_check(input: torch.Tensor, target: torch.Tensor, ignore_in
             "Class labels in `target` tensor cannot be larger than vocab_size minus one, "
             f"got vocab size of {input.size(2)} and target label of {int(torch.max(t))}."
         )
+
+
+def _perplexity_flag_raise(input: torch.Tensor, target: torch.Tensor, ignore_index: Optional[int]) -> None:
+    """K7 raised its device flag: a counted target lies outside [0, vocab_size)."""
+    _perplexity_label_check(input, target, ignore_index)
+    t = target[target.ne(ignore_index)] if ignore_index is not None else target
+    raise ValueError(
+        "Class labels in `target` tensor cannot be negative, "
+        f"got vocab size of {input.size(2)} and target label of {int(torch.min(t))}."
+    )
 
 
 def _perplexity_input_check(input: torch.Tensor, target: torch.Tensor, ignore_index: Optional[int] = None) -> None:
