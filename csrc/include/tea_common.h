@@ -67,24 +67,20 @@ __device__ __forceinline__ int wave_id() {
   return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
   return v;
 }
-__device__ __forceinline__ double wave_sum(double v) {
+// integers by comparison; float below keeps fmaxf (a NaN loses to a number)
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  for (int o = 32; o > 0; o >>= 1) {
+    const T y = __shfl_xor(v, o, kWave);
+    v = y > v ? y : v;
+  }
   return v;
 }
 __device__ __forceinline__ float wave_max(float v) {
@@ -95,6 +91,33 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+
+// lane l's double in every lane (two v_readlane; l wave-uniform)
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+  return __hiloint2double(hi, lo);
+}
+
+// DPP move of a double (two v_mov_dpp), 0 in the lanes and rows that receive nothing
+template <int Ctrl, int RowMask = 0xf>
+__device__ __forceinline__ double dpp_f64(double x) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), Ctrl, RowMask, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), Ctrl, RowMask, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+// inclusive prefix sum over the wave's 64 lanes (32- and 64-bit integers)
+template <typename T>
+__device__ __forceinline__ T wave_incl_sum(T v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const T u = __shfl_up(v, o, kWave);
+    if (lane >= o) v += u;
+  }
   return v;
 }
 

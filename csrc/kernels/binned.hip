@@ -382,16 +382,6 @@ __global__ __launch_bounds__(256) void binned_dense_reduce_kernel(const unsigned
   if (pos) atomicAdd(&acc[o + 1], pos);
 }
 
-__device__ __forceinline__ unsigned long long wave_incl_sum_u64(unsigned long long v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 // one block per class: replica sum per bin (self-cleaning) -> block-parallel suffix scan
 __global__ __launch_bounds__(kB) void binned_suffix_kernel(BinnedArgs a, int replicas) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -439,8 +429,8 @@ __global__ __launch_bounds__(kB) void binned_suffix_kernel(BinnedArgs a, int rep
     const int b = start - static_cast<int>(threadIdx.x);
     const unsigned long long p = b >= 1 ? s_pos[b] : 0ull;
     const unsigned long long f = b >= 1 ? s_neg[b] : 0ull;
-    const unsigned long long ip = wave_incl_sum_u64(p);
-    const unsigned long long ifp = wave_incl_sum_u64(f);
+    const unsigned long long ip = wave_incl_sum(p);
+    const unsigned long long ifp = wave_incl_sum(f);
     const int w = threadIdx.x >> 6;
     __syncthreads();
     if (lane_id() == 63) {

@@ -184,12 +184,6 @@ __device__ __forceinline__ void zero_tile(const ChArgs& a, int ti, int tj) {
   }
 }
 
-__device__ __forceinline__ double bcast(double x, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-  return __hiloint2double(hi, lo);
-}
-
 constexpr int kPB = 4;  // columns per elimination step of the diagonal-tile factorisation
 
 struct alignas(16) PotrfLds {

@@ -153,15 +153,6 @@ __device__ __forceinline__ uint32_t order_key(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, kWave);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
 // ---- top-k mode: row resident in registers, k packed-key wave maxima
 template <int KIND, int TK, int R>
 __global__ __launch_bounds__(kB) void ml_topk_kernel(MultilabelArgs a) {
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(kB) void ml_topk_kernel(MultilabelArgs a) {
           best = cand > best ? cand : best;
         }
       }
-      best = wave_max_u64(best);
+      best = wave_max(best);
       const uint32_t win = ~static_cast<uint32_t>(best & 0xffffffffull);
       if (static_cast<int>(win % kWave) == lane) sel |= 1u << (win / kWave);
     }
@@ -249,7 +240,7 @@ __global__ __launch_bounds__(kB) void ml_topk_vec_kernel(MultilabelArgs a) {
             best = cand > best ? cand : best;
           }
         }
-      best = wave_max_u64(best);
+      best = wave_max(best);
       const uint32_t win = ~static_cast<uint32_t>(best & 0xffffffffull);
       if (static_cast<int>((win % (kWave * 4)) / 4) == lane) sel |= 1u << ((win / (kWave * 4)) * 4 + win % 4);
     }

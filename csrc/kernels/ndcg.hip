@@ -75,13 +75,6 @@ __device__ __forceinline__ double gain_of(double t, int exponential) {
   return g > 0.0 ? g : 0.0;
 }
 
-__device__ __forceinline__ double readlane_f64(double v, int j) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane(static_cast<int>(b), j);
-  const int hi = __builtin_amdgcn_readlane(static_cast<int>(b >> 32), j);
-  return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
-}
-
 __device__ __forceinline__ double row_value(double dcg, double idcg, bool bad) {
   if (bad) return __builtin_nan("");
   return idcg == 0.0 ? 0.0 : dcg / idcg;

@@ -37,6 +37,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "tea_common.h"
 #include "tea_kernels.h"
 
 namespace tea {
@@ -98,10 +99,8 @@ __device__ __forceinline__ bool better(double v, int i, double bv, int bi) { ret
 
 template <int Ctrl>
 __device__ __forceinline__ void dpp_cand(double& v, int& i) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), Ctrl, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), Ctrl, 0xf, 0xf, false);
+  const double pv = dpp_f64<Ctrl>(v);
   const int pi = __builtin_amdgcn_update_dpp(0, i, Ctrl, 0xf, 0xf, false);
-  const double pv = __hiloint2double(hi, lo);
   if (better(pv, pi, v, i)) {
     v = pv;
     i = pi;

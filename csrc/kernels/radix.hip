@@ -161,7 +161,8 @@ __global__ __launch_bounds__(kRT) void radix_upsweep_kernel(RadixArgs a, const u
   for (int64_t q = (row * gridDim.x + tile) * kRT + threadIdx.x; q < cells; q += nb * kRT) prev[q] = 0u;
 }
 
-// Downsweep: wave w owns the contiguous sub-tile [w * 1024, (w + 1) * 1024) of the tile
+// ---- the pass body both sorts share (radix_downsweep_kernel, onesweep_pass_kernel).
+// Wave w owns the w-th contiguous quarter of the tile, from key wbase
 // (round j = 64 consecutive keys), so (wave, round, lane) IS the source order and every
 // wave ranks its keys with wave-private digit counters - no block barrier inside the loop.
 // Then: wave-ordered offsets + per-tile digit starts (one barrier), keys/values are placed in
@@ -169,27 +170,25 @@ __global__ __launch_bounds__(kRT) void radix_upsweep_kernel(RadixArgs a, const u
 // addresses of each digit run (coalesced; v1 scattered 4-byte writes straight to HBM).
 // VMODE: 0 = values from the previous pass, 1 = source index (pass 0), 2 = caller payload of
 // dtype PT (pass 0); separate instantiations keep the payload conversion out of passes 1-3
-template <int kRounds, int VMODE, typename PT = uint32_t, int KIND = 0>
-__global__ __launch_bounds__(kRT) void radix_downsweep_kernel(RadixArgs a, const uint32_t* keys_in,
-                                                              const uint32_t* vals_in, uint32_t* keys_out,
-                                                              uint32_t* vals_out, int pass) {
-  constexpr int kRTile = kRT * kRounds;
-  const int64_t row = blockIdx.y;
-  const int tile = blockIdx.x;
-  const int shift = 8 * pass;
-  const bool last = pass == 3;
-  constexpr int kSub = kRTile / kRWaves;  // keys per wave
-  __shared__ uint32_t base[kBins];        // global (row-relative) start of each digit's run
-  __shared__ uint32_t tstart[kBins];      // start of each digit inside the sorted tile
-  __shared__ uint32_t wc[kRWaves][kBins]; // per-wave digit counts -> per-wave offsets
-  __shared__ uint32_t wsum[kRWaves];
-  __shared__ uint32_t sk[kRTile], sv[kRTile];
-  const int lane = lane_id();
-  const int w = threadIdx.x >> 6;
-  const int64_t tbase = static_cast<int64_t>(tile) * kRTile;
-  const int64_t wbase = tbase + static_cast<int64_t>(w) * kSub;
-  uint32_t k[kRounds], v[kRounds], r[kRounds];
-  // clamped unconditional loads, tail masked afterwards (see load_tile)
+template <int kRounds>
+struct PassLds {  // the block's LDS arrays: TEA_PASS_LDS declares them in the kernel, separately (as
+                  // members of one __shared__ struct every pass kernel took 9-17 more address adds)
+  uint32_t (&base)[kBins];         // global (row-relative) start of each digit's run
+  uint32_t (&tstart)[kBins];       // start of each digit inside the sorted tile
+  uint32_t (&wc)[kRWaves][kBins];  // per-wave digit counts -> per-wave offsets
+  uint32_t (&wsum)[kRWaves];
+  uint32_t (&sk)[kRT * kRounds], (&sv)[kRT * kRounds];
+};
+#define TEA_PASS_LDS(s)                                                                         \
+  __shared__ uint32_t base[kBins], tstart[kBins], wc[kRWaves][kBins], wsum[kRWaves], sk[kRT * kRounds], \
+      sv[kRT * kRounds];                                                                        \
+  PassLds<kRounds> s { base, tstart, wc, wsum, sk, sv }
+
+// clamped unconditional loads, the tail masked afterwards by pass_mask_tail (see load_tile)
+template <int kRounds, int VMODE, typename PT, int KIND>
+__device__ __forceinline__ void pass_load(const RadixArgs& a, const uint32_t* keys_in, const uint32_t* vals_in,
+                                          int pass, int64_t row, int64_t wbase, int lane, uint32_t (&k)[kRounds],
+                                          uint32_t (&v)[kRounds]) {
 #pragma unroll
   for (int j = 0; j < kRounds; ++j) {
     const int64_t i = wbase + j * 64 + lane;
@@ -199,6 +198,12 @@ __global__ __launch_bounds__(kRT) void radix_downsweep_kernel(RadixArgs a, const
     else if constexpr (VMODE == 1) v[j] = static_cast<uint32_t>(i);
     else v[j] = first_payload<PT, KIND>(a, row, ic);
   }
+}
+
+// zeroes what pass_load read past the row's end, and this wave's digit counters
+template <int kRounds>
+__device__ __forceinline__ void pass_mask_tail(const RadixArgs& a, int64_t wbase, int lane, uint32_t (&k)[kRounds],
+                                               uint32_t (&v)[kRounds], uint32_t (&wc)[kBins]) {
 #pragma unroll
   for (int j = 0; j < kRounds; ++j) {
     const bool ok = wbase + j * 64 + lane < a.n;
@@ -206,7 +211,138 @@ __global__ __launch_bounds__(kRT) void radix_downsweep_kernel(RadixArgs a, const
     v[j] = ok ? v[j] : 0u;
   }
 #pragma unroll
-  for (int q = 0; q < kBins / 64; ++q) wc[w][lane + 64 * q] = 0;
+  for (int q = 0; q < kBins / 64; ++q) wc[lane + 64 * q] = 0;
+}
+
+// exclusive scan of one value x per thread over the block's 256 threads, given inc =
+// wave_incl_sum(x): the wave totals meet in wsum (one barrier; the caller fences a reuse of wsum)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t inc, uint32_t (&wsum)[kRWaves], int lane,
+                                                    int w) {
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  uint32_t off = 0;
+#pragma unroll
+  for (int q = 0; q < kRWaves; ++q)
+    if (q < w) off += wsum[q];
+  return off + inc - x;
+}
+
+// wave-local stable ranks (wave-private counters; a wave's LDS ops are in program order)
+template <int kRounds>
+__device__ __forceinline__ void pass_rank(const RadixArgs& a, int64_t wbase, int lane, int shift,
+                                          const uint32_t (&k)[kRounds], uint32_t (&wc)[kBins], uint32_t (&r)[kRounds]) {
+  const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+  for (int j = 0; j < kRounds; ++j) {
+    const bool valid = wbase + j * 64 + lane < a.n;
+    const uint64_t active = __ballot(valid);
+    const uint32_t d = (k[j] >> shift) & 0xffu;
+    const uint64_t peers = match_digit(d, active);
+    const uint64_t pb = peers & below;
+    r[j] = wc[d] + static_cast<uint32_t>(__popcll(pb));
+    if (valid && pb == 0ull)  // the lowest lane of the digit's peers advances its counter
+      wc[d] += static_cast<uint32_t>(__popcll(peers));
+  }
+}
+
+// thread t owns digit t: the waves' counts become their exclusive offsets; returns the tile's count
+__device__ __forceinline__ uint32_t pass_wave_offsets(uint32_t (&wc)[kRWaves][kBins], int t) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int q = 0; q < kRWaves; ++q) {
+    const uint32_t c = wc[q][t];
+    wc[q][t] = o;
+    o += c;
+  }
+  return o;
+}
+
+// keys / values into LDS in sorted tile order
+template <int kRounds>
+__device__ __forceinline__ void pass_place(const RadixArgs& a, PassLds<kRounds>& s, int64_t wbase, int lane, int w,
+                                           int shift, const uint32_t (&k)[kRounds], const uint32_t (&v)[kRounds],
+                                           const uint32_t (&r)[kRounds]) {
+#pragma unroll
+  for (int j = 0; j < kRounds; ++j) {
+    if (wbase + j * 64 + lane < a.n) {
+      const uint32_t d = (k[j] >> shift) & 0xffu;
+      const uint32_t p = s.tstart[d] + s.wc[w][d] + r[j];
+      s.sk[p] = k[j];
+      s.sv[p] = v[j];
+    }
+  }
+}
+
+// the sorted tile from LDS to each digit's run (the last pass: scores as floats + the payload);
+// returns whether the tile was a full one
+template <int kRounds>
+__device__ __forceinline__ bool pass_write_out(const RadixArgs& a, const PassLds<kRounds>& s, int64_t row,
+                                               int64_t tbase, int shift, bool last, uint32_t* keys_out,
+                                               uint32_t* vals_out) {
+  constexpr int kRTile = kRT * kRounds;
+  const int64_t tn64 = a.n - tbase;
+  const int tn = static_cast<int>(tn64 < kRTile ? tn64 : kRTile);
+  if (tn == kRTile) {
+    // full tile: every LDS read of the write-out issued before the dependent ones and all the
+    // stores after (a rolled loop paid sk -> base / tstart -> store round trips per element)
+    uint32_t kk[kRounds], vv[kRounds];
+    int32_t pb[kRounds];  // base - tile start of the element's digit (may be negative)
+#pragma unroll
+    for (int j = 0; j < kRounds; ++j) {
+      kk[j] = s.sk[threadIdx.x + j * kRT];
+      vv[j] = s.sv[threadIdx.x + j * kRT];
+    }
+#pragma unroll
+    for (int j = 0; j < kRounds; ++j) {
+      const uint32_t d = (kk[j] >> shift) & 0xffu;
+      pb[j] = static_cast<int32_t>(s.base[d]) - static_cast<int32_t>(s.tstart[d]);
+    }
+#pragma unroll
+    for (int j = 0; j < kRounds; ++j) {
+      const int64_t pos = row * a.n + static_cast<int64_t>(pb[j]) + (threadIdx.x + j * kRT);
+      if (last) {
+        a.out_sorted[pos] = key2f_desc(kk[j] ^ a.key_xor);
+        a.out_order[pos] = static_cast<int32_t>(vv[j]);
+      } else {
+        keys_out[pos] = kk[j];
+        vals_out[pos] = vv[j];
+      }
+    }
+    return true;
+  }
+  for (int p = threadIdx.x; p < tn; p += kRT) {
+    const uint32_t key = s.sk[p];
+    const uint32_t d = (key >> shift) & 0xffu;
+    const int64_t pos = row * a.n + s.base[d] + (p - s.tstart[d]);
+    if (last) {
+      a.out_sorted[pos] = key2f_desc(key ^ a.key_xor);
+      a.out_order[pos] = static_cast<int32_t>(s.sv[p]);
+    } else {
+      keys_out[pos] = key;
+      vals_out[pos] = s.sv[p];
+    }
+  }
+  return false;
+}
+
+// Downsweep: the shared pass body with digit bases from the upsweep's group and tile counts
+template <int kRounds, int VMODE, typename PT = uint32_t, int KIND = 0>
+__global__ __launch_bounds__(kRT) void radix_downsweep_kernel(RadixArgs a, const uint32_t* keys_in,
+                                                              const uint32_t* vals_in, uint32_t* keys_out,
+                                                              uint32_t* vals_out, int pass) {
+  constexpr int kRTile = kRT * kRounds;
+  const int64_t row = blockIdx.y;
+  const int tile = blockIdx.x;
+  const int shift = 8 * pass;
+  const bool last = pass == 3;
+  TEA_PASS_LDS(s);
+  const int lane = lane_id();
+  const int w = threadIdx.x >> 6;
+  const int64_t tbase = static_cast<int64_t>(tile) * kRTile;
+  const int64_t wbase = tbase + static_cast<int64_t>(w) * (kRTile / kRWaves);
+  uint32_t k[kRounds], v[kRounds], r[kRounds];
+  pass_load<kRounds, VMODE, PT, KIND>(a, keys_in, vals_in, pass, row, wbase, lane, k, v);
+  pass_mask_tail(a, wbase, lane, k, v, s.wc[w]);
   {  // digit bases = exclusive scan of the row's digit totals + this tile's prefix in the digit:
      // totals and the prefix of whole groups from the group counts, the rest from the tile
      // counts of this tile's own group (all independent, L2-resident loads)
@@ -236,113 +372,31 @@ __global__ __launch_bounds__(kRT) void radix_downsweep_kernel(RadixArgs a, const
     for (int q = 0; q < kGroup; ++q) hv[q] = q < in_group ? hv[q] : 0u;
 #pragma unroll
     for (int q = 0; q < kGroup; ++q) pre += hv[q];
+    // wave_incl_sum(tot), open-coded: through the helper the compiler unrolls the group loop above
+    // further (8 rounds: ~2170 -> ~3080 instructions and 36 B of scratch; 16 rounds: ~3370 -> ~4100
+    // and 129+ VGPRs, an occupancy step down; profiles/k3_pass_dedup_codegen.txt)
     uint32_t inc = tot;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const uint32_t u = __shfl_up(inc, o, 64);
       if (lane >= o) inc += u;
     }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q)
-      if (q < w) off += wsum[q];
-    base[threadIdx.x] = off + inc - tot + pre;
+    s.base[threadIdx.x] = block_excl_scan(tot, inc, s.wsum, lane, w) + pre;
   }
-  // wave-local stable ranks (wave-private counters; a wave's LDS ops are in program order)
-  const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    const bool valid = wbase + j * 64 + lane < a.n;
-    const uint64_t active = __ballot(valid);
-    const uint32_t d = (k[j] >> shift) & 0xffu;
-    const uint64_t peers = match_digit(d, active);
-    const uint64_t pb = peers & below;
-    r[j] = wc[w][d] + static_cast<uint32_t>(__popcll(pb));
-    if (valid && pb == 0ull)  // the lowest lane of the digit's peers advances its counter
-      wc[w][d] += static_cast<uint32_t>(__popcll(peers));
-  }
+  pass_rank(a, wbase, lane, shift, k, s.wc[w], r);
   __syncthreads();
-  {  // thread t owns digit t: per-wave exclusive offsets, tile count, tile-start scan
-    const int t = threadIdx.x;
-    uint32_t o = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q) {
-      const uint32_t c = wc[q][t];
-      wc[q][t] = o;
-      o += c;
-    }
-    uint32_t inc = o;
-#pragma unroll
-    for (int s2 = 1; s2 < 64; s2 <<= 1) {
-      const uint32_t u = __shfl_up(inc, s2, 64);
-      if (lane >= s2) inc += u;
-    }
+  {  // per-wave exclusive offsets, tile count, tile-start scan
+    const uint32_t o = pass_wave_offsets(s.wc, threadIdx.x);
+    const uint32_t inc = wave_incl_sum(o);
     __syncthreads();  // wsum reuse
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q)
-      if (q < w) off += wsum[q];
-    tstart[t] = off + inc - o;
+    s.tstart[threadIdx.x] = block_excl_scan(o, inc, s.wsum, lane, w);
   }
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    if (wbase + j * 64 + lane < a.n) {
-      const uint32_t d = (k[j] >> shift) & 0xffu;
-      const uint32_t p = tstart[d] + wc[w][d] + r[j];
-      sk[p] = k[j];
-      sv[p] = v[j];
-    }
-  }
+  pass_place(a, s, wbase, lane, w, shift, k, v, r);
   __syncthreads();
   if (last && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     *a.dirty = static_cast<uint32_t>(a.rows * a.ngroups * kBins);  // for the next sort's pass 0
-  const int64_t tn64 = a.n - tbase;
-  const int tn = static_cast<int>(tn64 < kRTile ? tn64 : kRTile);
-  if (tn == kRTile) {
-    // full tile: every LDS read of the write-out issued before the dependent ones and all the
-    // stores after (a rolled loop paid sk -> base / tstart -> store round trips per element)
-    uint32_t kk[kRounds], vv[kRounds];
-    int32_t pb[kRounds];  // base - tile start of the element's digit (may be negative)
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      kk[j] = sk[threadIdx.x + j * kRT];
-      vv[j] = sv[threadIdx.x + j * kRT];
-    }
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const uint32_t d = (kk[j] >> shift) & 0xffu;
-      pb[j] = static_cast<int32_t>(base[d]) - static_cast<int32_t>(tstart[d]);
-    }
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const int64_t pos = row * a.n + static_cast<int64_t>(pb[j]) + (threadIdx.x + j * kRT);
-      if (last) {
-        a.out_sorted[pos] = key2f_desc(kk[j] ^ a.key_xor);
-        a.out_order[pos] = static_cast<int32_t>(vv[j]);
-      } else {
-        keys_out[pos] = kk[j];
-        vals_out[pos] = vv[j];
-      }
-    }
-    return;
-  }
-  for (int p = threadIdx.x; p < tn; p += kRT) {
-    const uint32_t key = sk[p];
-    const uint32_t d = (key >> shift) & 0xffu;
-    const int64_t pos = row * a.n + base[d] + (p - tstart[d]);
-    if (last) {
-      a.out_sorted[pos] = key2f_desc(key ^ a.key_xor);
-      a.out_order[pos] = static_cast<int32_t>(sv[p]);
-    } else {
-      keys_out[pos] = key;
-      vals_out[pos] = sv[p];
-    }
-  }
+  pass_write_out(a, s, row, tbase, shift, last, keys_out, vals_out);
 }
 
 // ---------------------------------------------------------------- onesweep
@@ -446,18 +500,13 @@ __global__ __launch_bounds__(kRT) void onesweep_hist_kernel(RadixArgs a, int64_t
   }
 }
 
-// one pass: load + rank as radix_downsweep_kernel, then publish / look back, then scatter
+// one pass: the shared pass body around publish / look back
 template <int kRounds, int VMODE, typename PT = uint32_t, int KIND = 0>
 __global__ __launch_bounds__(kRT) void onesweep_pass_kernel(RadixArgs a, const uint32_t* keys_in,
                                                             const uint32_t* vals_in, uint32_t* keys_out,
                                                             uint32_t* vals_out, int pass) {
   constexpr int kRTile = kRT * kRounds;
-  constexpr int kSub = kRTile / kRWaves;
-  __shared__ uint32_t base[kBins];
-  __shared__ uint32_t tstart[kBins];
-  __shared__ uint32_t wc[kRWaves][kBins];
-  __shared__ uint32_t wsum[kRWaves];
-  __shared__ uint32_t sk[kRTile], sv[kRTile];
+  TEA_PASS_LDS(s);
   // tile id = blockIdx: workgroups are dispatched in order per XCD, so the lowest unfinished
   // tile only ever waits on finished ones.  (Ids from a counter ticket, the textbook guard,
   // cost 512 serialised same-address atomics per launch: 18.9 vs 13.2 us per pass at 1M,
@@ -470,70 +519,23 @@ __global__ __launch_bounds__(kRT) void onesweep_pass_kernel(RadixArgs a, const u
   const int lane = lane_id();
   const int w = threadIdx.x >> 6;
   const int64_t tbase = static_cast<int64_t>(tile) * kRTile;
-  const int64_t wbase = tbase + static_cast<int64_t>(w) * kSub;
+  const int64_t wbase = tbase + static_cast<int64_t>(w) * (kRTile / kRWaves);
   RDX_TRACE(0);
   uint32_t k[kRounds], v[kRounds], r[kRounds];
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    const int64_t i = wbase + j * 64 + lane;
-    const int64_t ic = i < a.n ? i : a.n - 1;
-    k[j] = load_key(a, keys_in, pass, row, ic);
-    if constexpr (VMODE == 0) v[j] = vals_in[row * a.n + ic];
-    else if constexpr (VMODE == 1) v[j] = static_cast<uint32_t>(i);
-    else v[j] = first_payload<PT, KIND>(a, row, ic);
-  }
+  pass_load<kRounds, VMODE, PT, KIND>(a, keys_in, vals_in, pass, row, wbase, lane, k, v);
   // the row's digit totals (histogram kernel) -> exclusive scan over the digits
   uint32_t gtot = 0;
 #pragma unroll
   for (int c = 0; c < kGCopies; ++c) gtot += a.os_g[((row * kGCopies + c) * 4 + pass) * kBins + threadIdx.x];
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    const bool ok = wbase + j * 64 + lane < a.n;
-    k[j] = ok ? k[j] : 0u;
-    v[j] = ok ? v[j] : 0u;
-  }
-#pragma unroll
-  for (int q = 0; q < kBins / 64; ++q) wc[w][lane + 64 * q] = 0;
-  uint32_t gb;
-  {
-    uint32_t inc = gtot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t off = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q)
-      if (q < w) off += wsum[q];
-    gb = off + inc - gtot;
-  }
-  // wave-local stable ranks (as radix_downsweep_kernel)
-  const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    const bool valid = wbase + j * 64 + lane < a.n;
-    const uint64_t active = __ballot(valid);
-    const uint32_t d = (k[j] >> shift) & 0xffu;
-    const uint64_t peers = match_digit(d, active);
-    const uint64_t pb = peers & below;
-    r[j] = wc[w][d] + static_cast<uint32_t>(__popcll(pb));
-    if (valid && pb == 0ull) wc[w][d] += static_cast<uint32_t>(__popcll(peers));
-  }
+  pass_mask_tail(a, wbase, lane, k, v, s.wc[w]);
+  const uint32_t gb = block_excl_scan(gtot, wave_incl_sum(gtot), s.wsum, lane, w);
+  pass_rank(a, wbase, lane, shift, k, s.wc[w], r);
   __syncthreads();
   RDX_TRACE(1);
   const int P = pass & 1;
   {  // thread t owns digit t
     const int t = threadIdx.x;
-    uint32_t o = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q) {
-      const uint32_t c = wc[q][t];
-      wc[q][t] = o;
-      o += c;
-    }
+    const uint32_t o = pass_wave_offsets(s.wc, t);
     // publish this tile's count (ready-flagged) and add it to the group's word
     const int ngroups = static_cast<int>(a.ngroups);
     uint32_t* st = a.os_status + P * a.os_splane + row * a.tiles * kBins;
@@ -542,12 +544,7 @@ __global__ __launch_bounds__(kRT) void onesweep_pass_kernel(RadixArgs a, const u
     os_put(st + static_cast<int64_t>(tile) * kBins + t, kReady | o);
     os_add64(ga + static_cast<int64_t>(g) * kBins + t, (1ull << 32) | o);
     RDX_TRACE(2);
-    uint32_t inc = o;
-#pragma unroll
-    for (int s2 = 1; s2 < 64; s2 <<= 1) {
-      const uint32_t u = __shfl_up(inc, s2, 64);
-      if (lane >= s2) inc += u;
-    }
+    const uint32_t inc = wave_incl_sum(o);
     // clear the planes the previous pass used (the next pass uses them), up to their extents
     {
       const int64_t nthr = static_cast<int64_t>(gridDim.x) * kRT;
@@ -593,78 +590,24 @@ __global__ __launch_bounds__(kRT) void onesweep_pass_kernel(RadixArgs a, const u
       }
     }
     if (spins >= a.spin_limit) a.os_hdr[8] = 1u;  // surfaced: K3 scans return NaN, the next sort warns
-    base[t] = gb + pre;
+    s.base[t] = gb + pre;
     // the last tile of the row: every tile of the row has consumed the digit totals
     if (last && tile == a.tiles - 1) {
 #pragma unroll
       for (int q = 0; q < kGCopies * 4; ++q) a.os_g[(row * kGCopies * 4 + q) * kBins + t] = 0u;
     }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
+    s.tstart[t] = block_excl_scan(o, inc, s.wsum, lane, w);
     RDX_TRACE(3);
-    uint32_t off = 0;
-#pragma unroll
-    for (int q = 0; q < kRWaves; ++q)
-      if (q < w) off += wsum[q];
-    tstart[t] = off + inc - o;
   }
   if (id == 0 && threadIdx.x == 0) {  // this pass's extents: the next pass clears them
     a.os_hdr[4 + P] = static_cast<uint32_t>(a.rows * a.tiles * kBins);
     a.os_hdr[6 + P] = static_cast<uint32_t>(a.rows * a.ngroups * kBins);
   }
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kRounds; ++j) {
-    if (wbase + j * 64 + lane < a.n) {
-      const uint32_t d = (k[j] >> shift) & 0xffu;
-      const uint32_t p = tstart[d] + wc[w][d] + r[j];
-      sk[p] = k[j];
-      sv[p] = v[j];
-    }
-  }
+  pass_place(a, s, wbase, lane, w, shift, k, v, r);
   __syncthreads();
   RDX_TRACE(4);
-  const int64_t tn64 = a.n - tbase;
-  const int tn = static_cast<int>(tn64 < kRTile ? tn64 : kRTile);
-  if (tn == kRTile) {
-    uint32_t kk[kRounds], vv[kRounds];
-    int32_t pb[kRounds];
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      kk[j] = sk[threadIdx.x + j * kRT];
-      vv[j] = sv[threadIdx.x + j * kRT];
-    }
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const uint32_t d = (kk[j] >> shift) & 0xffu;
-      pb[j] = static_cast<int32_t>(base[d]) - static_cast<int32_t>(tstart[d]);
-    }
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const int64_t pos = row * a.n + static_cast<int64_t>(pb[j]) + (threadIdx.x + j * kRT);
-      if (last) {
-        a.out_sorted[pos] = key2f_desc(kk[j] ^ a.key_xor);
-        a.out_order[pos] = static_cast<int32_t>(vv[j]);
-      } else {
-        keys_out[pos] = kk[j];
-        vals_out[pos] = vv[j];
-      }
-    }
-    RDX_TRACE(5);
-    return;
-  }
-  for (int p = threadIdx.x; p < tn; p += kRT) {
-    const uint32_t key = sk[p];
-    const uint32_t d = (key >> shift) & 0xffu;
-    const int64_t pos = row * a.n + base[d] + (p - tstart[d]);
-    if (last) {
-      a.out_sorted[pos] = key2f_desc(key ^ a.key_xor);
-      a.out_order[pos] = static_cast<int32_t>(sv[p]);
-    } else {
-      keys_out[pos] = key;
-      vals_out[pos] = sv[p];
-    }
-  }
+  if (pass_write_out(a, s, row, tbase, shift, last, keys_out, vals_out)) RDX_TRACE(5);
 }
 
 // [n, C] row-major -> [C, n] (LDS-tiled 64 x 64 transpose; coalesced both ways)
@@ -750,38 +693,46 @@ int launch_transpose_f32(const float* in, int64_t n, int64_t c, int64_t ld_in, f
 
 namespace {
 
-template <int R>
-int radix_passes(const RadixArgs& a, hipStream_t stream) {
-  const dim3 grid(static_cast<unsigned>(a.tiles), static_cast<unsigned>(a.rows));
+// launches pass p of either sort (the upsweep / downsweep pair, or the onesweep pass): owns the
+// key / value ping-pong and the pass-0 payload instantiations
+template <bool kOnesweep, int R>
+int launch_pass(const RadixArgs& a, dim3 grid, int p, hipStream_t stream) {
   const uint32_t* kin[4] = {nullptr, a.keys0, a.keys1, a.keys0};
   const uint32_t* vin[4] = {nullptr, a.vals0, a.vals1, a.vals0};
   uint32_t* kout[4] = {a.keys0, a.keys1, a.keys0, nullptr};
   uint32_t* vout[4] = {a.vals0, a.vals1, a.vals0, nullptr};
-  for (int p = 0; p < 4; ++p) {
-    hipLaunchKernelGGL(radix_upsweep_kernel<R>, grid, dim3(kRT), 0, stream, a, kin[p], p);
-#define TEA_DOWNSWEEP(...) \
-  hipLaunchKernelGGL((radix_downsweep_kernel<R, __VA_ARGS__>), grid, dim3(kRT), 0, stream, a, kin[p], vin[p], kout[p], vout[p], p)
-    if (p > 0) {
-      TEA_DOWNSWEEP(0);
-    } else if (a.payload_kind == 0) {
-      TEA_DOWNSWEEP(1);
-    } else if (a.payload_kind == 1) {
-      switch (a.payload_dt) {
-        case DType::f32: TEA_DOWNSWEEP(2, float, 1); break;
-        case DType::i64: TEA_DOWNSWEEP(2, int64_t, 1); break;
-        case DType::i32: TEA_DOWNSWEEP(2, int32_t, 1); break;
-        case DType::u8: case DType::b8: TEA_DOWNSWEEP(2, uint8_t, 1); break;
-        default: return -2;
-      }
-    } else {
-      switch (a.payload_dt) {
-        case DType::i64: TEA_DOWNSWEEP(2, int64_t, 2); break;
-        case DType::i32: TEA_DOWNSWEEP(2, int32_t, 2); break;
-        default: return -2;
-      }
+  if constexpr (!kOnesweep) hipLaunchKernelGGL(radix_upsweep_kernel<R>, grid, dim3(kRT), 0, stream, a, kin[p], p);
+#define TEA_PASS(...)                                                                                            \
+  hipLaunchKernelGGL((kOnesweep ? onesweep_pass_kernel<R, __VA_ARGS__> : radix_downsweep_kernel<R, __VA_ARGS__>), \
+                     grid, dim3(kRT), 0, stream, a, kin[p], vin[p], kout[p], vout[p], p)
+  if (p > 0) {
+    TEA_PASS(0);
+  } else if (a.payload_kind == 0) {
+    TEA_PASS(1);
+  } else if (a.payload_kind == 1) {
+    switch (a.payload_dt) {
+      case DType::f32: TEA_PASS(2, float, 1); break;
+      case DType::i64: TEA_PASS(2, int64_t, 1); break;
+      case DType::i32: TEA_PASS(2, int32_t, 1); break;
+      case DType::u8: case DType::b8: TEA_PASS(2, uint8_t, 1); break;
+      default: return -2;
     }
-#undef TEA_DOWNSWEEP
+  } else {
+    switch (a.payload_dt) {
+      case DType::i64: TEA_PASS(2, int64_t, 2); break;
+      case DType::i32: TEA_PASS(2, int32_t, 2); break;
+      default: return -2;
+    }
   }
+#undef TEA_PASS
+  return 0;
+}
+
+template <int R>
+int radix_passes(const RadixArgs& a, hipStream_t stream) {
+  const dim3 grid(static_cast<unsigned>(a.tiles), static_cast<unsigned>(a.rows));
+  for (int p = 0; p < 4; ++p)
+    if (const int rc = launch_pass<false, R>(a, grid, p, stream)) return rc;
   return static_cast<int>(hipGetLastError());
 }
 
@@ -800,34 +751,8 @@ int radix_onesweep(const RadixArgs& a, hipStream_t stream) {
   const dim3 hgrid(static_cast<unsigned>((a.n + per - 1) / per), static_cast<unsigned>(a.rows));
   hipLaunchKernelGGL(onesweep_hist_kernel, hgrid, dim3(kRT), 0, stream, a, per);
   const dim3 grid(static_cast<unsigned>(a.rows * a.tiles));
-  const uint32_t* kin[4] = {nullptr, a.keys0, a.keys1, a.keys0};
-  const uint32_t* vin[4] = {nullptr, a.vals0, a.vals1, a.vals0};
-  uint32_t* kout[4] = {a.keys0, a.keys1, a.keys0, nullptr};
-  uint32_t* vout[4] = {a.vals0, a.vals1, a.vals0, nullptr};
-  for (int p = 0; p < 4; ++p) {
-#define TEA_PASS(...) \
-  hipLaunchKernelGGL((onesweep_pass_kernel<R, __VA_ARGS__>), grid, dim3(kRT), 0, stream, a, kin[p], vin[p], kout[p], vout[p], p)
-    if (p > 0) {
-      TEA_PASS(0);
-    } else if (a.payload_kind == 0) {
-      TEA_PASS(1);
-    } else if (a.payload_kind == 1) {
-      switch (a.payload_dt) {
-        case DType::f32: TEA_PASS(2, float, 1); break;
-        case DType::i64: TEA_PASS(2, int64_t, 1); break;
-        case DType::i32: TEA_PASS(2, int32_t, 1); break;
-        case DType::u8: case DType::b8: TEA_PASS(2, uint8_t, 1); break;
-        default: return -2;
-      }
-    } else {
-      switch (a.payload_dt) {
-        case DType::i64: TEA_PASS(2, int64_t, 2); break;
-        case DType::i32: TEA_PASS(2, int32_t, 2); break;
-        default: return -2;
-      }
-    }
-#undef TEA_PASS
-  }
+  for (int p = 0; p < 4; ++p)
+    if (const int rc = launch_pass<true, R>(a, grid, p, stream)) return rc;
   return static_cast<int>(hipGetLastError());
 }
 

@@ -137,15 +137,6 @@ __global__ __launch_bounds__(kRB) void retrieval_scatter_kernel(RetrievalArgs a)
   }
 }
 
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t y = __shfl_xor(v, o, kWave);
-    v = y > v ? y : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kRB) void retrieval_select_kernel(RetrievalArgs a) {
   const int64_t q = static_cast<int64_t>(blockIdx.x) * (kRB / kWave) + (threadIdx.x >> 6);
   if (q >= a.Q) return;  // whole wave
@@ -172,7 +163,7 @@ __global__ __launch_bounds__(kRB) void retrieval_select_kernel(RetrievalArgs a) 
       const uint64_t pk = (static_cast<uint64_t>(a.rec_key[s0 + j]) << 32) | static_cast<uint32_t>(~pos);
       if (pk < prev && pk > best) best = pk;
     }
-    best = wave_max_u64(best);
+    best = wave_max(best);
     prev = best;
     if (lane == r) {
       const uint32_t pos = ~static_cast<uint32_t>(best & 0xffffffffu);

@@ -40,6 +40,7 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "tea_common.h"
 #include "tea_kernels.h"
 
 namespace tea {
@@ -108,13 +109,6 @@ __device__ __forceinline__ double as_double(unsigned long long b) {
   return __longlong_as_double(static_cast<long long>(b));
 }
 
-template <int Ctrl>
-__device__ __forceinline__ double dpp_f64(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), Ctrl, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), Ctrl, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-
 // Sum of each 16-lane row of a wave, in every lane of the row: DPP quad swaps, half-row and
 // row mirrors (a few cycles per step instead of an LDS-latency ds_bpermute).
 __device__ __forceinline__ double row16_sum(double x) {
@@ -159,21 +153,14 @@ __device__ __forceinline__ double tree_partials(const double* scratch, int i) {
   return p[0];
 }
 
-template <int Ctrl, int RowMask>
-__device__ __forceinline__ double dpp_f64_rows(double x) {  // 0 in the rows RowMask leaves out
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), Ctrl, RowMask, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), Ctrl, RowMask, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-
 template <int N, int NT = kThreads>
 __device__ __forceinline__ void block_sum(double (&v)[N], double* scratch) {
   if constexpr (N == 1) {
     // one value: the wave total by DPP (row sums, then row_bcast:15 / row_bcast:31 into lane
     // 63), so the tree below adds NT / 64 wave partials instead of NT / 16 row partials
     double x = row16_sum(v[0]);
-    x += dpp_f64_rows<0x142, 0xa>(x);
-    x += dpp_f64_rows<0x143, 0xc>(x);
+    x += dpp_f64<0x142, 0xa>(x);
+    x += dpp_f64<0x143, 0xc>(x);
     if ((threadIdx.x & 63) == 63) scratch[threadIdx.x >> 6] = x;
     __syncthreads();
     constexpr int NP = NT / 64;
@@ -560,12 +547,6 @@ __global__ __launch_bounds__(NT) void tridiag_kernel(const double* __restrict__ 
 // redundantly from it (DPP sums), the tile products p = M v reduce over the 16 lanes of a tile
 // row (DPP), tau p goes through LDS (barrier), p . v reduces over a tile row's column tiles,
 // then the rank-2 update M -= v w^T + w v^T in registers.
-// a lane's double in every lane (two readlanes)
-__device__ __forceinline__ double lane_f64(double x, int l) {
-  const long long b = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 template <int TR>
 __global__ __launch_bounds__(16 * kTail / TR) void symeig_tail_kernel(const double* __restrict__ tail, int n,
                                                                       double* d_out, double* e_out) {
@@ -601,7 +582,7 @@ __global__ __launch_bounds__(16 * kTail / TR) void symeig_tail_kernel(const doub
       for (int b = 0; b < 8; ++b) cc[b] = col[cb * 8 + b];
       const double cj = col[j];
       double sg = row16_sum((l >= j + 2 ? x0 * x0 : 0.0) + (l + 64 >= j + 2 ? x1 * x1 : 0.0));
-      sg = (lane_f64(sg, 0) + lane_f64(sg, 16)) + (lane_f64(sg, 32) + lane_f64(sg, 48));
+      sg = (readlane_f64(sg, 0) + readlane_f64(sg, 16)) + (readlane_f64(sg, 32) + readlane_f64(sg, 48));
       const double alpha = col[j + 1];
       SYM_TT(j, 1);
       double tau, beta, scale;
