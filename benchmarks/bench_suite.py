@@ -250,6 +250,15 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.spearman_corrcoef(x, y)
         return make
 
+    def calibration(cls):
+        def make():
+            x, t = torch.randn(B, C, device=dev) * 3, randint(C, B)
+            if cls:
+                m = M.MulticlassCalibrationError(from_logits=True, device=dev)
+                return lambda: m.update(x, t)
+            return lambda: F.multiclass_calibration_error(x, t, from_logits=True)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -399,6 +408,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "r2_score 8192x1000": r2,
         "spearman_corrcoef N=1M (K3a + K14)": spearman(False),
         "SpearmanCorrCoef.compute N=1M (K3a + K14)": spearman(True),
+        "multiclass_calibration_error logits 8192x1000 (K15)": calibration(False),
+        "MulticlassCalibrationError.update logits 8192x1000 (K15)": calibration(True),
         "Sum.update 8192x1000 (K5b)": k5b(M.Sum, "sum"),
         "Mean.update 8192x1000 (K5b)": k5b(M.Mean, "sum"),
         "PeakSignalNoiseRatio.update 8192x1000 (K5b)": k5b(M.PeakSignalNoiseRatio, "psnr"),

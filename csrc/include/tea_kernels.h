@@ -675,3 +675,40 @@ int64_t rank_corr_pitch(int64_t n);
 int rank_moments_blocks(int64_t n);
 int launch_rank_corr(const RankCorrArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K15: multiclass calibration error (csrc/kernels/calibration.hip).  One pass over [n, c] scores
+// finds each row's argmax and confidence (the row maximum, or 1 / sum exp(x - max) for logits) and
+// folds (count, correct, confidence) into n_bins bins whose edges are float32(b / n_bins).
+// kCalibMaxBins: a 4-wave block holds 4 wave-private bin sets (u32 count, u32 correct, f64
+// confidence: 64 B per bin) plus the edge table, 17 KiB at the cap, so the 8 blocks a CU can hold
+// at full occupancy fit its 160 KiB of LDS.
+constexpr int kCalibMaxBins = 256;
+constexpr int kCalibMaxBlocks = 1024;  // grid cap of the row launch, both arms
+constexpr int kCalibNarrowMaxC = 32;   // a thread owns a row up to here, a wave above
+struct CalibrationArgs {
+  const void* input = nullptr;  // [n, c] f32 / f16 / bf16, unit column stride, element-aligned rows
+  DType in_dt = DType::f32;
+  int64_t row_stride = 0;       // elements
+  const void* target = nullptr; // [n] int64 / int32, contiguous
+  DType tg_dt = DType::i64;
+  int64_t n = 0;
+  int64_t c = 0;                // 1 .. 2^31 - 1
+  int n_bins = 0;               // 1 .. kCalibMaxBins
+  int from_logits = 0;
+  int* err = nullptr;           // bit 0: target outside [0, c); bit 1: confidence outside [0, 1]
+  double* partial = nullptr;    // [calibration_blocks(n, c), 3, n_bins] scratch
+  // the finish launch: dst[s][b] (+)= the partials of state s (count, correct, confidence) added in
+  // block order; `accumulate` 0 overwrites (the functional's scratch triple).  With `out`, the same
+  // launch then evaluates the value from dst
+  double* dst[3] = {nullptr, nullptr, nullptr};
+  int accumulate = 0;
+  int norm = 0;                 // 0: l1 (ECE), 1: max (MCE), 2: l2
+  float* out = nullptr;
+};
+int calibration_blocks(int64_t n, int64_t c);  // grid of the row launch = number of partial triples
+int launch_calibration(const CalibrationArgs& a, hipStream_t stream);
+// the value of three [n_bins] float64 states, by one wave
+int launch_calibration_value(const double* bin_count, const double* correct_sum, const double* conf_sum, int n_bins,
+                             int norm, float* out, hipStream_t stream);
+}  // namespace tea

@@ -124,6 +124,7 @@ enum class Scratch : int {
   kSsimPartials = 14,       // K12
   kNdcgPartials = 15,       // K13
   kRankCorrPartials = 16,   // K14
+  kCalibrationPartials = 17,  // K15
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

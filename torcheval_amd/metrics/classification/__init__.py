@@ -18,6 +18,8 @@ from torcheval_amd.metrics.classification.binned_precision_recall_curve import (
     MulticlassBinnedPrecisionRecallCurve,
     MultilabelBinnedPrecisionRecallCurve,
 )
+# not a reference name: imported, kept out of __all__ (the top-level list is built from it)
+from torcheval_amd.metrics.classification.calibration_error import MulticlassCalibrationError  # noqa: F401
 from torcheval_amd.metrics.classification.confusion_matrix import (
     BinaryConfusionMatrix,
     MulticlassConfusionMatrix,

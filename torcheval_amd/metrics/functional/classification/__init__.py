@@ -27,6 +27,10 @@ from torcheval_amd.metrics.functional.classification.binned_precision_recall_cur
     multiclass_binned_precision_recall_curve,
     multilabel_binned_precision_recall_curve,
 )
+# not a reference name: imported, kept out of __all__ (the top-level list is built from it)
+from torcheval_amd.metrics.functional.classification.calibration_error import (  # noqa: F401
+    multiclass_calibration_error,
+)
 from torcheval_amd.metrics.functional.classification.confusion_matrix import (
     binary_confusion_matrix,
     multiclass_confusion_matrix,
