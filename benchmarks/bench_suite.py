@@ -250,6 +250,15 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.spearman_corrcoef(x, y)
         return make
 
+    def pearson(cls):
+        def make():
+            x, y = rand(B, C).t(), rand(B, C).t()  # [outputs, n] views of [n, outputs] predictions
+            if cls:
+                m = M.PearsonCorrCoef(num_tasks=C, device=dev)
+                return lambda: m.update(x, y)
+            return lambda: F.pearson_corrcoef(x, y, num_tasks=C)
+        return make
+
     def calibration(cls):
         def make():
             x, t = torch.randn(B, C, device=dev) * 3, randint(C, B)
@@ -408,6 +417,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "r2_score 8192x1000": r2,
         "spearman_corrcoef N=1M (K3a + K14)": spearman(False),
         "SpearmanCorrCoef.compute N=1M (K3a + K14)": spearman(True),
+        "pearson_corrcoef 8192x1000 .t() (K16)": pearson(False),
+        "PearsonCorrCoef.update 8192x1000 .t() (K16)": pearson(True),
         "multiclass_calibration_error logits 8192x1000 (K15)": calibration(False),
         "MulticlassCalibrationError.update logits 8192x1000 (K15)": calibration(True),
         "Sum.update 8192x1000 (K5b)": k5b(M.Sum, "sum"),

@@ -712,3 +712,38 @@ int launch_calibration(const CalibrationArgs& a, hipStream_t stream);
 int launch_calibration_value(const double* bin_count, const double* correct_sum, const double* conf_sum, int n_bins,
                              int norm, float* out, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K16: Pearson and concordance correlation per task (csrc/kernels/corrcoef.hip) from six FP64
+// moments per task, the rows of a [6, tasks] state: n, mean_x, mean_y, m2_x, m2_y, c_xy
+// (docs/parity.md, "Not in the reference").  A batch's moments are formed from five sums of
+// differences to the task's first sample and merged into the state by the pairwise update.
+constexpr int kCorrRowSpan = 4096;  // samples of one task a row-arm block owns
+constexpr int kCorrColSpan = 128;   // samples (of 64 tasks each) a column-arm block owns
+constexpr int kCorrColTasks = 64;   // task columns of a column-arm block, one per lane
+struct CorrcoefArgs {
+  // element (task, i) of an operand is at task * task_stride + i * sample_stride (elements).
+  // Row arm: sample strides 1, any task strides.  Column arm: task strides 1.
+  const void* x = nullptr;      // f32 / f16 / bf16, element-aligned
+  const void* y = nullptr;
+  DType x_dt = DType::f32;
+  DType y_dt = DType::f32;
+  int64_t x_task_stride = 0, x_sample_stride = 1;
+  int64_t y_task_stride = 0, y_sample_stride = 1;
+  int64_t tasks = 0;
+  int64_t n = 0;                // samples per task, >= 1
+  int column = 0;               // 0: row arm, 1: column arm
+  double* partial = nullptr;    // [tasks, corrcoef_blocks(n, column), 5] scratch: S_x, S_y, S_xx, S_yy, S_xy
+  // the finish launch: with `moments`, the batch merges into that [6, tasks] state in place;
+  // with `out`, out[task] <- the batch's value (concordance 0: Pearson, 1: Lin's concordance)
+  double* moments = nullptr;
+  float* out = nullptr;
+  int concordance = 0;
+};
+int corrcoef_blocks(int64_t n, int column);  // partials per task
+int launch_corrcoef(const CorrcoefArgs& a, hipStream_t stream);
+// state[6, tasks] <- its pairwise merge with other[6, tasks]; one launch
+int launch_corrcoef_merge(double* state, const double* other, int64_t tasks, hipStream_t stream);
+// out[task] <- the value of state[6, tasks]; one launch
+int launch_corrcoef_value(const double* state, int64_t tasks, int concordance, float* out, hipStream_t stream);
+}  // namespace tea

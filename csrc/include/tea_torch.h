@@ -125,6 +125,7 @@ enum class Scratch : int {
   kNdcgPartials = 15,       // K13
   kRankCorrPartials = 16,   // K14
   kCalibrationPartials = 17,  // K15
+  kCorrcoefPartials = 18,   // K16
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

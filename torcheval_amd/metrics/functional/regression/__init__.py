@@ -8,6 +8,7 @@ from torcheval_amd.metrics.functional.regression.mean_squared_error import (
     _mean_squared_error_update_input_check,
     _mean_squared_error_param_check,
 )
+from torcheval_amd.metrics.functional.regression.pearson import concordance_corrcoef, pearson_corrcoef
 from torcheval_amd.metrics.functional.regression.r2_score import (
     r2_score,
     _r2_score_update,
@@ -18,7 +19,9 @@ from torcheval_amd.metrics.functional.regression.r2_score import (
 from torcheval_amd.metrics.functional.regression.spearman import spearman_corrcoef
 
 __all__ = [
+    "concordance_corrcoef",
     "mean_squared_error",
+    "pearson_corrcoef",
     "r2_score",
     "spearman_corrcoef",
 ]

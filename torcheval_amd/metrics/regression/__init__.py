@@ -1,11 +1,14 @@
 """Regression class metrics (parity: metrics/regression/*.py)."""
 
 from torcheval_amd.metrics.regression.mean_squared_error import MeanSquaredError
+from torcheval_amd.metrics.regression.pearson import ConcordanceCorrCoef, PearsonCorrCoef
 from torcheval_amd.metrics.regression.r2_score import R2Score
 from torcheval_amd.metrics.regression.spearman import SpearmanCorrCoef
 
 __all__ = [
+    "ConcordanceCorrCoef",
     "MeanSquaredError",
+    "PearsonCorrCoef",
     "R2Score",
     "SpearmanCorrCoef",
 ]
