@@ -5,6 +5,7 @@
 //  * loads are 16 B per lane (Guideline 13): float4 for f32, 8 x 16-bit for bf16/f16.
 //  * kernels take raw pointers + a DType tag; the pybind layer (csrc/bindings/) owns the
 //    torch::Tensor plumbing so kernel TUs compile in seconds (no torch headers here).
+//  * kernels templated on the score dtype (KIND 0 / 1 / 2 = f32 / bf16 / f16) read rows through tea_rowload.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

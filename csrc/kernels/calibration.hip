@@ -21,6 +21,7 @@
 // is counted nowhere else and sets a bit of ``err``, the only atomic.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -31,8 +32,6 @@ constexpr int kWpb = kB / kWave;
 constexpr int kFinishThreads = 1024;
 constexpr int kNoIndex = 0x7fffffff;
 
-__device__ __forceinline__ float fmaximum(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-
 // e^x to about an ulp for x <= 0 (x = -inf gives 0, NaN stays NaN): v_exp_f32 of x * log2(e) with
 // the product's rounding error and the constant's put back to first order.  The plain fast form
 // loses |x| * 2^-24 relative to it, which shows in the confidence at the tolerance the tests hold.
@@ -42,45 +41,6 @@ __device__ __forceinline__ float exp_neg(float x) {
   const float lost = __builtin_fmaf(x, kL2e, -t) + x * kL2eLo;
   const float e = __builtin_amdgcn_exp2f(t);
   return x == -__builtin_huge_valf() ? 0.f : __builtin_fmaf(e, lost * kLn2, e);
-}
-
-// exponents are taken against 0 while the maximum is still -inf (K7's rule): exp(-inf - 0) = 0
-__device__ __forceinline__ float finite_or_zero(float m) { return m == -__builtin_huge_valf() ? 0.f : m; }
-
-template <int KIND>
-__device__ __forceinline__ float load1(const void* row, int64_t col) {
-  if constexpr (KIND == 0) return static_cast<const float*>(row)[col];
-  const uint16_t b = static_cast<const uint16_t*>(row)[col];
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
-
-// 16 values from a 16-B aligned address: four 16-B loads of f32, two of 16-bit values
-template <int KIND>
-__device__ __forceinline__ void load16(const void* p, int64_t col, float (&v)[16]) {
-  if constexpr (KIND == 0) {
-    const float4* q = reinterpret_cast<const float4*>(static_cast<const float*>(p) + col);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float4 x = q[u];
-      v[4 * u] = x.x;
-      v[4 * u + 1] = x.y;
-      v[4 * u + 2] = x.z;
-      v[4 * u + 3] = x.w;
-    }
-  } else {
-    const uint4* q = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(p) + col);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const uint4 x = q[u];
-      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint16_t lo = static_cast<uint16_t>(w[e] & 0xffffu), hi = static_cast<uint16_t>(w[e] >> 16);
-        v[8 * u + 2 * e] = KIND == 1 ? bf16_to_f32(lo) : f16_to_f32(lo);
-        v[8 * u + 2 * e + 1] = KIND == 1 ? bf16_to_f32(hi) : f16_to_f32(hi);
-      }
-    }
-  }
 }
 
 // What a lane (or the thread that owns a row) knows of the columns it has seen, which it meets in
@@ -180,7 +140,6 @@ __device__ __forceinline__ void bins_store(const Bins& s, int nb, double* partia
 template <int KIND, bool LOGITS>
 __global__ __launch_bounds__(kB) void calibration_wave_kernel(CalibrationArgs a) {
   __shared__ Bins s;
-  constexpr int ELS = KIND == 0 ? 4 : 2;
   constexpr int64_t kStep = kWave * 16;
   const int nb = a.n_bins;
   bins_init(s, nb);
@@ -188,26 +147,26 @@ __global__ __launch_bounds__(kB) void calibration_wave_kernel(CalibrationArgs a)
   const int C = static_cast<int>(a.c);
   const int64_t nw = static_cast<int64_t>(gridDim.x) * kWpb;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWpb + w; row < a.n; row += nw) {
-    const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELS;
+    const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     const int64_t t = load_as_i64(a.target, a.tg_dt, row);
     RowState st;
-    int head = static_cast<int>(((16u - (reinterpret_cast<uintptr_t>(rp) & 15u)) & 15u) / ELS);
+    int head = static_cast<int>(head_elems<KIND>(rp));
     if (head > C) head = C;
     const int64_t body = ((C - head) / 16) * 16;
     if (lane < head) absorb1<LOGITS>(load1<KIND>(rp, lane), lane, st);
-    const char* bp = rp + head * ELS;  // 16-B aligned
+    const char* bp = rp + head * kind_bytes<KIND>;  // 16-B aligned
     int64_t base = static_cast<int64_t>(lane) * 16;
     // two steps loaded before either is reduced: rows too long for the batch to fill the CUs
     for (; base + kStep < body; base += 2 * kStep) {
       float v0[16], v1[16];
-      load16<KIND>(bp, base, v0);
-      load16<KIND>(bp, base + kStep, v1);
+      load_vals<KIND>(bp, base, v0);
+      load_vals<KIND>(bp, base + kStep, v1);
       absorb16<LOGITS>(v0, head + static_cast<int>(base), st);
       absorb16<LOGITS>(v1, head + static_cast<int>(base + kStep), st);
     }
     for (; base < body; base += kStep) {
       float v0[16];
-      load16<KIND>(bp, base, v0);
+      load_vals<KIND>(bp, base, v0);
       absorb16<LOGITS>(v0, head + static_cast<int>(base), st);
     }
     const int64_t tc = head + body + lane;
@@ -241,7 +200,6 @@ __global__ __launch_bounds__(kB) void calibration_wave_kernel(CalibrationArgs a)
 template <int KIND, bool LOGITS>
 __global__ __launch_bounds__(kB) void calibration_thread_kernel(CalibrationArgs a) {
   __shared__ Bins s;
-  constexpr int ELS = KIND == 0 ? 4 : 2;
   const int nb = a.n_bins;
   bins_init(s, nb);
   const int lane = lane_id(), w = wave_id();
@@ -255,7 +213,7 @@ __global__ __launch_bounds__(kB) void calibration_thread_kernel(CalibrationArgs 
     int bin = -1, flags = 0;
     bool correct = false;
     if (live) {
-      const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELS;
+      const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
       const int64_t t = load_as_i64(a.target, a.tg_dt, row);
       RowState st;
       for (int c = 0; c < C; ++c) absorb1<false>(load1<KIND>(rp, c), c, st);

@@ -29,6 +29,7 @@
 #include "tea_common.h"
 #include "tea_fold.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -38,15 +39,6 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kChunkLoads = 4;  // 16-B loads per lane per row chunk
 constexpr int kNarrowMaxC = 32;
-
-__device__ __forceinline__ float fmaximum(float a, float b) {
-  return __builtin_elementwise_maximum(a, b);
-}
-
-template <int KIND>
-__device__ __forceinline__ float h16(uint16_t b) {
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
 
 // KIND 0: f32 (VEC 4 or 1); KIND 1: bf16, KIND 2: f16 (VEC 8 or 1)
 template <int KIND, int VEC>
@@ -61,15 +53,18 @@ __device__ __forceinline__ void load_vec(const void* row, int col, float (&v)[VE
   } else if constexpr (KIND == 0) {
     v[0] = static_cast<const float*>(row)[col];
   } else if constexpr (VEC == 8) {
+    // K1's own unpack, both converts nested: through load_vals of tea_rowload.h (both halves cut
+    // out first) five bf16 kernels order their instructions differently
+    // (profiles/rowload_dedup_codegen.txt)
     const uint4 x = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(row) + col);
     const uint32_t w[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v[2 * e] = h16<KIND>(static_cast<uint16_t>(w[e] & 0xffffu));
-      v[2 * e + 1] = h16<KIND>(static_cast<uint16_t>(w[e] >> 16));
+      v[2 * e] = widen16<KIND>(static_cast<uint16_t>(w[e] & 0xffffu));
+      v[2 * e + 1] = widen16<KIND>(static_cast<uint16_t>(w[e] >> 16));
     }
   } else {
-    v[0] = h16<KIND>(static_cast<const uint16_t*>(row)[col]);
+    v[0] = load1<KIND>(row, col);
   }
 }
 
@@ -122,12 +117,6 @@ __device__ __forceinline__ void unal_fix_tail(float (&v)[N][4], int base, int C,
       for (int e = 0; e < 4; ++e) v[u][e] = me ? r[e] : v[u][e];
     }
   }
-}
-
-template <int KIND>
-__device__ __forceinline__ float load_one(const void* row, int64_t col) {
-  if constexpr (KIND == 0) return static_cast<const float*>(row)[col];
-  return h16<KIND>(static_cast<const uint16_t*>(row)[col]);
 }
 
 __device__ __forceinline__ int64_t load_target(const void* tgt, DType dt, int64_t i) {
@@ -210,7 +199,7 @@ __device__ __noinline__ int row_argmax_exact(const void* rp, int C, int lane) {
   float bv = -__builtin_huge_valf();
   int bi = 0x7fffffff;
   for (int col = lane; col < C; col += kWave) {
-    const float v = load_one<KIND>(rp, col);
+    const float v = load1<KIND>(rp, col);
     if (argmax_better(v, col, bv, bi)) {
       bv = v;
       bi = col;
@@ -252,7 +241,6 @@ template <int KIND, int VEC, bool TOPK, bool PRED = true, bool UNAL = false>
 __device__ __forceinline__ void cls_wide_body(const ClsCountsArgs& a) {
   const int lane = lane_id();
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   constexpr int STEP = kWave * VEC;             // columns per wave-load
   constexpr int CHUNK = STEP * kChunkLoads;     // columns per chunk
   const int C = static_cast<int>(a.c);
@@ -261,7 +249,7 @@ __device__ __forceinline__ void cls_wide_body(const ClsCountsArgs& a) {
 
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id(); row < a.n;
        row += nwaves) {
-    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELSIZE;
+    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     bool correct;
     int64_t pred = -1;
     int64_t t;
@@ -363,7 +351,7 @@ __device__ __forceinline__ void cls_wide_body(const ClsCountsArgs& a) {
     } else {
       t = load_target(a.target, a.tg_dt, row);
       const bool t_ok = t >= 0 && t < C;
-      const float xt = t_ok ? load_one<KIND>(rp, t) : __builtin_nanf("");
+      const float xt = t_ok ? load1<KIND>(rp, t) : __builtin_nanf("");
       int cnt = 0;
       float nx[kChunkLoads][VEC];
       load_chunk<KIND, VEC, UNAL>(rp, 0, C, lane, nx);
@@ -443,12 +431,11 @@ __device__ __forceinline__ void micro_rows(const void* __restrict__ input, const
   constexpr int VEC = KIND == 0 ? 4 : 8;
   constexpr int NV = kChunkLoads * VEC;  // values per lane
   constexpr int STEP = kWave * VEC;      // columns per wave-load
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   typedef typename RowVals<NV>::type vec_t;
   const int lane = lane_id();
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id(); row < n; row += nwaves) {
-    const char* rp = static_cast<const char*>(input) + row * row_stride * ELSIZE;
+    const char* rp = static_cast<const char*>(input) + row * row_stride * kind_bytes<KIND>;
     float f[kChunkLoads][VEC];
 #pragma unroll
     for (int u = 0; u < kChunkLoads; ++u) load_row_vec<KIND, VEC, UNAL>(rp, u * STEP + lane * VEC, C, f[u]);
@@ -554,18 +541,18 @@ __device__ __forceinline__ bool micro_row(const MicroPendArgs& a, const char* __
 
 template <int KIND, typename TGT, int WPB, bool UNAL>
 __global__ __launch_bounds__(WPB * kWave) void cls_micro_pend_kernel(MicroPendArgs a) {
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   const int lane = lane_id();
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * WPB;
   // the wave's first row is loaded unconditionally (clamped to the last row), so nothing
   // branches on `n` before the loads and every kernel argument arrives in one scalar round trip
   const int64_t row0 = static_cast<int64_t>(blockIdx.x) * WPB + wave_id();
   const int64_t r0 = row0 < a.n ? row0 : a.n - 1;  // the launcher guarantees n >= 1
-  const bool c0 = micro_row<KIND, TGT, UNAL>(a, static_cast<const char*>(a.input) + r0 * a.row_stride * ELSIZE,
-                                       static_cast<const TGT*>(a.target)[r0], lane);
+  const bool c0 =
+      micro_row<KIND, TGT, UNAL>(a, static_cast<const char*>(a.input) + r0 * a.row_stride * kind_bytes<KIND>,
+                                 static_cast<const TGT*>(a.target)[r0], lane);
   uint32_t correct_acc = (row0 < a.n && c0) ? 1u : 0u;
   for (int64_t row = row0 + nwaves; row < a.n; row += nwaves) {
-    const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELSIZE;
+    const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     correct_acc += micro_row<KIND, TGT, UNAL>(a, rp, static_cast<const TGT*>(a.target)[row], lane);
   }
   // deferred fold: one no-return atomic per wave into one of 64 pending cells, no LDS, no
@@ -599,7 +586,6 @@ __global__ __launch_bounds__(kBlock) void cls_wide_kernel(ClsCountsArgs a) {
 // Narrow rows (C <= 32): one thread per row, class histograms privatised in LDS.
 template <int KIND, bool TOPK>
 __global__ __launch_bounds__(kBlock) void cls_narrow_kernel(ClsCountsArgs a) {
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   __shared__ float s_correct[kNarrowMaxC], s_label[kNarrowMaxC], s_pred[kNarrowMaxC];
   __shared__ float s_fp[kNarrowMaxC];
   __shared__ float s_conf[kNarrowMaxC * kNarrowMaxC];
@@ -619,7 +605,7 @@ __global__ __launch_bounds__(kBlock) void cls_narrow_kernel(ClsCountsArgs a) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; row < a.n;
        row += stride) {
-    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELSIZE;
+    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     const int64_t t = load_target(a.target, a.tg_dt, row);
     bool correct;
     int64_t pred = -1;
@@ -627,7 +613,7 @@ __global__ __launch_bounds__(kBlock) void cls_narrow_kernel(ClsCountsArgs a) {
       float bv = -__builtin_huge_valf();
       int bi = 0x7fffffff;
       for (int c = 0; c < C; ++c) {
-        const float v = load_one<KIND>(rp, c);
+        const float v = load1<KIND>(rp, c);
         if (argmax_better(v, c, bv, bi)) {
           bv = v;
           bi = c;
@@ -637,9 +623,9 @@ __global__ __launch_bounds__(kBlock) void cls_narrow_kernel(ClsCountsArgs a) {
       correct = pred == t;
     } else {
       const bool t_ok = t >= 0 && t < C;
-      const float xt = t_ok ? load_one<KIND>(rp, t) : __builtin_nanf("");
+      const float xt = t_ok ? load1<KIND>(rp, t) : __builtin_nanf("");
       int cnt = 0;
-      for (int c = 0; c < C; ++c) cnt += load_one<KIND>(rp, c) > xt;
+      for (int c = 0; c < C; ++c) cnt += load1<KIND>(rp, c) > xt;
       correct = t_ok && cnt < a.k;
     }
     correct_acc += correct;

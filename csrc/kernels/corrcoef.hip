@@ -23,6 +23,7 @@
 // its own task's m2 NaN through the arithmetic (inf - inf^2 / n) and touches no other task.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -36,16 +37,6 @@ constexpr int kColUnroll = 8;
 // at 1000 x 8192 (profiles/pearson_r12.json)
 static_assert(kCorrRowSpan == 8 * 2 * kB, "the row arm's span is two groups of 8 per thread");
 static_assert(kCorrColSpan % (kWpb * kColUnroll) == 0, "a column-arm wave walks whole unrolled steps");
-
-template <int KIND>
-constexpr int els() { return KIND == 0 ? 4 : 2; }
-
-template <int KIND>
-__device__ __forceinline__ double load1(const void* base, int64_t i) {
-  if constexpr (KIND == 0) return static_cast<double>(static_cast<const float*>(base)[i]);
-  const uint16_t b = static_cast<const uint16_t*>(base)[i];
-  return static_cast<double>(KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b));
-}
 
 // eight consecutive samples as loaded, before any convert
 template <int KIND>
@@ -86,13 +77,7 @@ __device__ __forceinline__ void widen8(const Raw8<KIND>& r, double (&v)[8]) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = static_cast<double>(f[e]);
   } else {
-    const uint32_t w[4] = {r.w.x, r.w.y, r.w.z, r.w.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint16_t lo = static_cast<uint16_t>(w[e] & 0xffffu), hi = static_cast<uint16_t>(w[e] >> 16);
-      v[2 * e] = static_cast<double>(KIND == 1 ? bf16_to_f32(lo) : f16_to_f32(lo));
-      v[2 * e + 1] = static_cast<double>(KIND == 1 ? bf16_to_f32(hi) : f16_to_f32(hi));
-    }
+    unpack8<KIND>(r.w, v);
   }
 }
 
@@ -100,7 +85,7 @@ __device__ __forceinline__ void widen8(const Raw8<KIND>& r, double (&v)[8]) {
 template <int KIND>
 __device__ __forceinline__ int head_of(const void* p) {
   if constexpr (KIND == 0) return 0;
-  return static_cast<int>(((16u - (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / 2u);
+  return static_cast<int>(head_elems<KIND>(p));
 }
 
 // the five sums of differences to the pivot
@@ -130,15 +115,15 @@ __global__ __launch_bounds__(kB) void corr_row_kernel(CorrcoefArgs a, int bpt) {
   __shared__ double s_w[kWpb][5];
   const int64_t task = blockIdx.x / bpt;
   const int b = blockIdx.x % bpt;
-  const char* xr = static_cast<const char*>(a.x) + task * a.x_task_stride * els<KX>();
-  const char* yr = static_cast<const char*>(a.y) + task * a.y_task_stride * els<KY>();
+  const char* xr = static_cast<const char*>(a.x) + task * a.x_task_stride * kind_bytes<KX>;
+  const char* yr = static_cast<const char*>(a.y) + task * a.y_task_stride * kind_bytes<KY>;
   const double px = load1<KX>(xr, 0), py = load1<KY>(yr, 0);
   const int64_t s0 = static_cast<int64_t>(b) * kCorrRowSpan;
   const int64_t left = a.n - s0;
   const int len = static_cast<int>(left < kCorrRowSpan ? left : kCorrRowSpan);
   // one head for both operands: the first 16-bit operand's; a second 16-bit operand with another
   // head takes element loads
-  const int hx = head_of<KX>(xr + s0 * els<KX>()), hy = head_of<KY>(yr + s0 * els<KY>());
+  const int hx = head_of<KX>(xr + s0 * kind_bytes<KX>), hy = head_of<KY>(yr + s0 * kind_bytes<KY>);
   int head = KX != 0 ? hx : hy;
   const bool yvec = KX == 0 || KY == 0 || hx == hy;
   head = head < len ? head : len;

@@ -16,6 +16,7 @@
 #include "tea_common.h"
 #include "tea_fold.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -54,13 +55,9 @@ __device__ __forceinline__ uint32_t row_correct(const RowFlags& f, int criteria)
   }
 }
 
-template <int KIND>
-__device__ __forceinline__ float ld_x(const void* p, int64_t i) {
-  if constexpr (KIND == 0) return static_cast<const float*>(p)[i];
-  const uint16_t b = static_cast<const uint16_t*>(p)[i];
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
-
+// four scores from element i (&p[i] aligned to 4 elements): one 16-B load of f32, one 8-B load of
+// 16-bit values.  Kept here: through unpack2 of tea_rowload.h 34 of the vectorised kernels order
+// their instructions differently (profiles/rowload_dedup_codegen.txt).
 template <int KIND>
 __device__ __forceinline__ void ld_x4(const void* p, int64_t i, float (&v)[4]) {
   if constexpr (KIND == 0) {
@@ -71,7 +68,7 @@ __device__ __forceinline__ void ld_x4(const void* p, int64_t i, float (&v)[4]) {
     const uint16_t h[4] = {static_cast<uint16_t>(q.x), static_cast<uint16_t>(q.x >> 16),
                            static_cast<uint16_t>(q.y), static_cast<uint16_t>(q.y >> 16)};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = KIND == 1 ? bf16_to_f32(h[e]) : f16_to_f32(h[e]);
+    for (int e = 0; e < 4; ++e) v[e] = widen16<KIND>(h[e]);
   }
 }
 
@@ -138,19 +135,12 @@ __global__ __launch_bounds__(kB) void ml_threshold_kernel(MultilabelArgs a) {
       }
     } else {
       for (int64_t c = lane; c < a.c; c += kWave)
-        f.add(ld_x<KIND>(a.x, xo + c) < a.threshold ? 0.f : 1.f, ld_t<TK>(a.t, to + c));
+        f.add(load1<KIND>(a.x, xo + c) < a.threshold ? 0.f : 1.f, ld_t<TK>(a.t, to + c));
     }
     const uint32_t r = row_correct(f, a.criteria);
     if (lane == 0) mine += r;
   }
   block_fold(a, mine);
-}
-
-__device__ __forceinline__ uint32_t order_key(float v) {
-  uint32_t u = __float_as_uint(v);
-  if (v != v) u = 0x7fc00000u;  // canonical NaN: above +inf after the flip
-  if (v == 0.f) u = 0u;         // -0.0 == +0.0: one key for both zeros
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // ---- top-k mode: row resident in registers, k packed-key wave maxima
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(kB) void ml_topk_kernel(MultilabelArgs a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t j = lane + static_cast<int64_t>(kWave) * r;
-      key[r] = j < a.c ? order_key(ld_x<KIND>(a.x, xo + j)) : 0u;
+      key[r] = j < a.c ? order_key(load1<KIND>(a.x, xo + j)) : 0u;
       tv[r] = j < a.c ? ld_t<TK>(a.t, to + j) : 0.f;
     }
     uint32_t sel = 0;
@@ -260,10 +250,9 @@ __global__ __launch_bounds__(kB) void ml_topk_vec_kernel(MultilabelArgs a) {
 
 template <int KIND, int TK>
 int launch_kinds(const MultilabelArgs& a, int grid, hipStream_t s) {
-  const int xes = KIND == 0 ? 4 : 2;
   const int tes = TK == 0 ? 4 : TK == 1 ? 8 : TK == 2 ? 4 : 1;
   const bool vec = a.c % 4 == 0 && a.x_row_stride % 4 == 0 && a.t_row_stride % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(a.x) % (4 * xes) == 0 &&
+                   reinterpret_cast<uintptr_t>(a.x) % (4 * kind_bytes<KIND>) == 0 &&
                    reinterpret_cast<uintptr_t>(a.t) % (4 * tes < 16 ? 4 * tes : 16) == 0;
   if (a.k > 0 && vec && a.c <= 8 * kWave * 4) {
     const int64_t RV = (a.c + kWave * 4 - 1) / (kWave * 4);

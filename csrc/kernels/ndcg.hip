@@ -8,7 +8,7 @@
 // The tie-averaged DCG needs, per item i, g_i = #{j : s_j > s_i} and e_i = #{j : s_j == s_i}:
 //     DCG = sum_i gain_i * (D[min(g_i + e_i, K)] - D[min(g_i, K)]) / e_i
 // with D the prefix table of the discounts (K + 1 doubles, built on the host).  IDCG is the same
-// functional with the gain as the score.  Scores compare by the order key of multilabel.hip
+// functional with the gain as the score.  Scores compare by order_key of tea_rowload.h
 // (-0.0 == +0.0, every NaN one key above +inf); gains, terms and sums are FP64.
 //
 //  * C <= 64: one wave per row, one item per lane.  g and e come from a C-step loop that
@@ -28,6 +28,7 @@
 // and n into ``num_rows``: no atomics on the value path, no host synchronisation, deterministic.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -37,24 +38,9 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxGrid = 2048;
 
-// descending-order key of a score: -0.0 == +0.0, all NaNs one key above +inf, never 0
-__device__ __forceinline__ uint32_t order_key(float v) {
-  uint32_t u = __float_as_uint(v);
-  if (v != v) u = 0x7fc00000u;
-  if (v == 0.f) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <int KIND>
-__device__ __forceinline__ float ld_score(const void* row, int col) {
-  if constexpr (KIND == 0) return static_cast<const float*>(row)[col];
-  const uint16_t b = static_cast<const uint16_t*>(row)[col];
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
-
 template <int KIND>
 __device__ __forceinline__ const void* score_row(const NdcgArgs& a, int64_t row) {
-  return static_cast<const char*>(a.x) + row * a.x_stride * (KIND == 0 ? 4 : 2);
+  return static_cast<const char*>(a.x) + row * a.x_stride * kind_bytes<KIND>;
 }
 
 __device__ __forceinline__ int dt_size(DType dt) {
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void ndcg_narrow_kernel(NdcgArgs a) {
     uint32_t key = 0u;
     double t = 0.0;
     if (live) {
-      key = order_key(ld_score<KIND>(score_row<KIND>(a, row), lane));
+      key = order_key(load1<KIND>(score_row<KIND>(a, row), lane));
       t = load_as_f64(static_cast<const char*>(a.t) + row * a.t_stride * tsize, a.t_dt, lane);
     }
     const bool bad = __any(live && !(t >= 0.0));
@@ -175,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void ndcg_wide_kernel(NdcgArgs a, int P) {
         const double t = load_as_f64(tr, a.t_dt, i);
         bad |= !(t >= 0.0);
         const double gain = gain_of(t, a.exponential);
-        kc = (static_cast<unsigned long long>(order_key(ld_score<KIND>(xr, i))) << 32) | static_cast<unsigned>(i);
+        kc = (static_cast<unsigned long long>(order_key(load1<KIND>(xr, i))) << 32) | static_cast<unsigned>(i);
         gb = static_cast<unsigned long long>(__double_as_longlong(gain));
       }
       s_key[i] = kc;

@@ -13,6 +13,7 @@
 // reference's host-synchronising max() check.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 #include <cstdlib>
 
@@ -22,48 +23,6 @@ namespace {
 
 constexpr int kB = 256;
 constexpr int kWpb = kB / kWave;
-
-template <int KIND>
-__device__ __forceinline__ void load8(const void* row, int64_t col, float (&v)[8]);
-
-template <>
-__device__ __forceinline__ void load8<0>(const void* row, int64_t col, float (&v)[8]) {
-  const float4* p = reinterpret_cast<const float4*>(static_cast<const float*>(row) + col);
-  const float4 a = p[0], b = p[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <int KIND>
-__device__ __forceinline__ void load8_16(const void* row, int64_t col, float (&v)[8]) {
-  const uint4 x = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(row) + col);
-  const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint16_t lo = static_cast<uint16_t>(w[e] & 0xffffu), hi = static_cast<uint16_t>(w[e] >> 16);
-    v[2 * e] = KIND == 1 ? bf16_to_f32(lo) : f16_to_f32(lo);
-    v[2 * e + 1] = KIND == 1 ? bf16_to_f32(hi) : f16_to_f32(hi);
-  }
-}
-template <>
-__device__ __forceinline__ void load8<1>(const void* row, int64_t col, float (&v)[8]) {
-  load8_16<1>(row, col, v);
-}
-template <>
-__device__ __forceinline__ void load8<2>(const void* row, int64_t col, float (&v)[8]) {
-  load8_16<2>(row, col, v);
-}
-
-template <int KIND>
-__device__ __forceinline__ float load1(const void* row, int64_t col) {
-  if constexpr (KIND == 0) return static_cast<const float*>(row)[col];
-  const uint16_t b = static_cast<const uint16_t*>(row)[col];
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
-
-// -inf logits are masked entries (probability 0); a NaN or +inf logit makes the row's sum NaN.
-// Where a maximum is still -inf, the exponent is taken against 0 instead: exp(-inf - 0) = 0 where
-// exp(-inf - -inf) would be NaN, and a NaN value or sum still reaches s.
-__device__ __forceinline__ float finite_or_zero(float mx) { return mx == -__builtin_huge_valf() ? 0.f : mx; }
 
 __device__ __forceinline__ void combine(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
@@ -96,9 +55,9 @@ __device__ __forceinline__ void absorb(const float (&v)[H][8], float& m, float& 
 template <int KIND>
 __device__ __forceinline__ void chunk16(const void* p, int64_t base, int64_t n, float& m, float& s) {
   float v[2][8];
-  load8<KIND>(p, base, v[0]);
+  load_vals<KIND>(p, base, v[0]);
   if (base + 8 < n) {
-    load8<KIND>(p, base + 8, v[1]);
+    load_vals<KIND>(p, base + 8, v[1]);
   } else {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[1][e] = -__builtin_huge_valf();
@@ -116,10 +75,10 @@ __device__ __forceinline__ void stream_row(const void* p, int64_t n, int lane, f
   if constexpr (U2) {
     for (; base + step < n; base += 2 * step) {
       float v[4][8];
-      load8<KIND>(p, base, v[0]);
-      load8<KIND>(p, base + 8, v[1]);
-      load8<KIND>(p, base + step, v[2]);
-      load8<KIND>(p, base + step + 8, v[3]);
+      load_vals<KIND>(p, base, v[0]);
+      load_vals<KIND>(p, base + 8, v[1]);
+      load_vals<KIND>(p, base + step, v[2]);
+      load_vals<KIND>(p, base + step + 8, v[3]);
       absorb<4>(v, m, s);
     }
   }
@@ -128,28 +87,26 @@ __device__ __forceinline__ void stream_row(const void* p, int64_t n, int lane, f
 
 // VEC: every row starts 16-B aligned and V % 16 == 0.  Otherwise (odd vocabularies such as
 // GPT-2's 50257, or row strides that break 16-B alignment) each row is split into a scalar head
-// up to the next 16-B boundary (< 16 / ELS values, one per lane), a 16-B-load body of whole
+// up to the next 16-B boundary (head_elems values, one per lane), a 16-B-load body of whole
 // 16-value chunks and a scalar tail (< 16 values); rows are element-aligned (checked on the host).
 template <int KIND, bool VEC, bool U2>
 __global__ __launch_bounds__(kB) void perplexity_kernel(PerplexityArgs a) {
   const int lane = lane_id();
   const int64_t nw = static_cast<int64_t>(gridDim.x) * kWpb;
-  constexpr int ELS = KIND == 0 ? 4 : 2;
   double acc = 0.0, cnt = 0.0;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWpb + wave_id(); row < a.rows; row += nw) {
     const int64_t t = load_as_i64(a.target, a.tg_dt, row * a.tg_stride);
     if (a.has_ignore && t == a.ignore_index) continue;
-    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELS;
+    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     float m = -__builtin_huge_valf(), s = 0.f;
     if constexpr (VEC) {
       stream_row<KIND, U2>(rp, a.v, lane, m, s);
     } else {
-      const uintptr_t addr = reinterpret_cast<uintptr_t>(rp);
-      int64_t head = static_cast<int64_t>(((16u - (addr & 15u)) & 15u) / ELS);
+      int64_t head = head_elems<KIND>(rp);
       if (head > a.v) head = a.v;
       const int64_t nb = ((a.v - head) / 16) * 16;
       if (lane < head) combine(m, s, load1<KIND>(rp, lane), 1.f);
-      const void* bp = static_cast<const char*>(rp) + head * ELS;
+      const void* bp = static_cast<const char*>(rp) + head * kind_bytes<KIND>;
       stream_row<KIND, U2>(bp, nb, lane, m, s);
       const int64_t c = head + nb + lane;
       if (c < a.v) combine(m, s, load1<KIND>(rp, c), 1.f);

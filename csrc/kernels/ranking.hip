@@ -15,6 +15,7 @@
 // and bit 0 of ``err`` is set (surfaced by the metric at compute / under validate).
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_rowload.h"
 
 namespace tea {
 
@@ -24,13 +25,6 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kChunkLoads = 4;
 
-template <int KIND>
-__device__ __forceinline__ float ld1(const void* row, int64_t col) {
-  if constexpr (KIND == 0) return static_cast<const float*>(row)[col];
-  const uint16_t b = static_cast<const uint16_t*>(row)[col];
-  return KIND == 1 ? bf16_to_f32(b) : f16_to_f32(b);
-}
-
 // count of v > xt over VEC consecutive columns starting at col (16-B load)
 template <int KIND, int VEC>
 __device__ __forceinline__ int gt_vec(const void* row, int col, float xt) {
@@ -38,18 +32,14 @@ __device__ __forceinline__ int gt_vec(const void* row, int col, float xt) {
     const float4 x = *reinterpret_cast<const float4*>(static_cast<const float*>(row) + col);
     return (x.x > xt) + (x.y > xt) + (x.z > xt) + (x.w > xt);
   } else if constexpr (VEC == 8) {
-    const uint4 x = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(row) + col);
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+    float v[8];
+    load_vals<KIND>(row, col, v);
     int c = 0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint16_t lo = static_cast<uint16_t>(w[e] & 0xffffu), hi = static_cast<uint16_t>(w[e] >> 16);
-      c += ((KIND == 1 ? bf16_to_f32(lo) : f16_to_f32(lo)) > xt);
-      c += ((KIND == 1 ? bf16_to_f32(hi) : f16_to_f32(hi)) > xt);
-    }
+    for (int e = 0; e < 8; ++e) c += v[e] > xt;
     return c;
   } else {
-    return ld1<KIND>(row, col) > xt;
+    return load1<KIND>(row, col) > xt;
   }
 }
 
@@ -60,7 +50,6 @@ __device__ __forceinline__ float score_of(int mode, int64_t rank, int k) {
 
 template <int KIND, int VEC>
 __global__ __launch_bounds__(kBlock) void rank_wide_kernel(RankArgs a) {
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   constexpr int STEP = kWave * VEC;
   constexpr int CHUNK = STEP * kChunkLoads;
   const int lane = lane_id();
@@ -68,10 +57,10 @@ __global__ __launch_bounds__(kBlock) void rank_wide_kernel(RankArgs a) {
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id(); row < a.n;
        row += nwaves) {
-    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELSIZE;
+    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     const int64_t t = load_as_i64(a.target, a.tg_dt, row);
     const bool t_ok = t >= 0 && t < C;
-    const float xt = ld1<KIND>(rp, t_ok ? t : 0);
+    const float xt = load1<KIND>(rp, t_ok ? t : 0);
     int cnt = 0;
     for (int base = 0; base < C; base += CHUNK) {
       int part[kChunkLoads];
@@ -93,15 +82,14 @@ __global__ __launch_bounds__(kBlock) void rank_wide_kernel(RankArgs a) {
 
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void rank_narrow_kernel(RankArgs a) {
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; row < a.n; row += stride) {
-    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * ELSIZE;
+    const void* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
     const int64_t t = load_as_i64(a.target, a.tg_dt, row);
     const bool t_ok = t >= 0 && t < a.c;
-    const float xt = ld1<KIND>(rp, t_ok ? t : 0);
+    const float xt = load1<KIND>(rp, t_ok ? t : 0);
     int cnt = 0;
-    for (int col = 0; col < a.c; ++col) cnt += ld1<KIND>(rp, col) > xt;
+    for (int col = 0; col < a.c; ++col) cnt += load1<KIND>(rp, col) > xt;
     a.out[row] = t_ok ? score_of(a.mode, cnt, a.k) : __builtin_nanf("");
     if (!t_ok && a.err) atomicOr(a.err, 1);
   }
@@ -117,8 +105,7 @@ int launch_wide(const RankArgs& a, hipStream_t s) {
 
 template <int KIND>
 int launch_kind(const RankArgs& a, hipStream_t s) {
-  constexpr int ELSIZE = KIND == 0 ? 4 : 2;
-  constexpr int VEC = 16 / ELSIZE;
+  constexpr int VEC = 16 / kind_bytes<KIND>;
   if (a.c < kWave) {
     int64_t blocks = (a.n + kBlock - 1) / kBlock;
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);

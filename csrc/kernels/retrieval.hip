@@ -27,6 +27,10 @@ constexpr int kRB = 256;       // hist / scatter block
 constexpr int kRPer = 16;      // samples per thread in hist / scatter
 constexpr int kRTile = kRB * kRPer;
 
+// order_key of tea_rowload.h with the zero test on the bit pattern, the same key.  Kept here:
+// through the shared spelling (v == 0.f) retrieval_scatter_kernel goes from 1005 to 989
+// instructions and retrieval_select_kernel from 32 to 31 SGPRs, untimed
+// (profiles/rowload_dedup_codegen.txt).
 __device__ __forceinline__ uint32_t order_key(float v) {
   uint32_t b = __float_as_uint(v);
   if (v != v) b = 0x7fc00000u;  // canonical +NaN: above +inf

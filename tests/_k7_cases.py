@@ -490,6 +490,12 @@ def _make_cases() -> List[Case]:
             add("targets", f"{tag}_ignore0", dt, edit=pad_with(0), expect="finite", ignore_index=0, **lay)
             add("targets", f"{tag}_all_ignored", dt, edit=all_rows(7), expect="nan", ignore_index=7, **lay)
 
+        # ---- the split walk on plain logits at the smallest shape that reaches all of it: columns
+        # 1:2086 of a [5, 2087] buffer.  Five rows are one more than a block's waves; the odd stride
+        # gives every row another head; the body of 2064 or 2080 values runs the two-step loop in
+        # every lane and the single step in the low ones, and a tail is left
+        add("walk", "v2085o1", dt, dtype=dt, b=1, s=5, v=2085, off=1, pad=1, edit=plain, expect="finite")
+
         # ---- the arms without the unrolled body (rows > 16384, short rows), four rows per wave of
         # the capped grid; v = 33 is a contiguous split arm whose rows have every head length
         tall = dict(dtype=dt, b=2, s=8200, expect="finite")

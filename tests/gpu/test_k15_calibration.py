@@ -169,6 +169,22 @@ def test_shapes_alignments_and_dtypes(dtype, logits, native_calls):
 
 
 @pytest.mark.parametrize("logits", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+def test_wave_walk_head_both_body_loops_and_tail(dtype, logits, native_calls):
+    """The smallest shape that reaches every part of the wave arm's walk: columns 1:2086 of a
+    [5, 2087] buffer.  Five rows are one more than a block's waves; the odd stride gives every row
+    another head; the body of 2064 or 2080 values runs the two-step loop in every lane and the single
+    step in the low ones, and a tail is left."""
+    x, t = scores(5, 2085, 2085, logits, dtype)
+    wide = torch.zeros(5, 2087, dtype=dtype, device=DEV)
+    wide[:, 1:2086] = x.to(DEV)
+    view = wide[:, 1:2086]
+    assert view.data_ptr() % 16 != 0 and view.stride(0) == 2087
+    check(view, t.to(DEV), x, t, 15, logits)
+    assert len(native_calls) == 4
+
+
+@pytest.mark.parametrize("logits", [False, True])
 @pytest.mark.parametrize("c", [2, 33])
 def test_more_rows_than_one_launch_covers(c, logits, native_calls):
     n = K.rows_per_launch(c) + 7

@@ -6,7 +6,9 @@ cases tell the arithmetic before the masked-logit fix from the rule is asserted 
 tests/metrics/text/test_k7_oracle.py.  Finite expectations are held to the tolerance of the other
 K7 tests (rel 2e-5 against float64); ``+inf`` and NaN expectations are compared by category.
 
-Against the kernel as it was before the fix, 158 of these 696 tests fail, in the functional, the
+Against the kernel as it was before the fix, 158 of these tests fail (of the 696 without the ``walk``
+group, plain logits at the smallest shape that reaches every part of the split walk, which came
+with the shared row loaders and was not run on that kernel), in the functional, the
 class and the deterministic test alike: every masked case whose ``old`` is "nan" (NaN for a finite
 perplexity: ``mask_vec`` v3072_leftover, v4096_last2100, v4096_pair2, v4112_keep3; ``mask_split``
 every ``_body`` case, v50257o3_keep3 and two float16 v1001 ``_keep3`` draws; ``no_u2`` v33_masked

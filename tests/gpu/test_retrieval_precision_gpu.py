@@ -71,6 +71,24 @@ def test_k10b_state_matches_sort_path(k, Q, monkeypatch):
     torch.testing.assert_close(nat.compute(), ref.compute(), equal_nan=True)
 
 
+def test_k10b_negative_zero_ties_positive_zero():
+    """One query, 8 samples, every zero inside the top k: -0.0 and +0.0 are one key, so the six
+    zeros keep their batch order (seen in the distinct targets and in the sign bits)."""
+    x = torch.tensor([0.0, -0.0, -1.0, -0.0, 0.0, -2.0, 0.0, -0.0])
+    t = torch.arange(1.0, 9.0)
+    m = RetrievalPrecision(k=8, num_queries=1, device=DEV)
+    m.update(x.to(DEV), t.to(DEV))
+    order = [0, 1, 3, 4, 6, 7, 2, 5]
+    assert int(m.count[0]) == 8
+    assert m.target[0].cpu().tolist() == t[order].tolist()
+    got = m.topk[0].cpu()
+    assert got.tolist() == x[order].tolist() and torch.equal(torch.signbit(got), torch.signbit(x[order]))
+    # a second batch: old entries come before new ones of the same key
+    m.update(torch.tensor([-0.0, 0.0], device=DEV), torch.tensor([9.0, 10.0], device=DEV))
+    assert m.target[0].cpu().tolist() == [1.0, 2.0, 4.0, 5.0, 7.0, 8.0, 9.0, 10.0]
+    assert torch.signbit(m.topk[0].cpu()).tolist() == [False, True, True, False, False, True, True, False]
+
+
 @pytest.mark.parametrize("k,Q", [(1, 1), (5, 3), (64, 37)])
 def test_k10b_ties_keep_cat_order(k, Q):
     """Ties (quantised scores, NaN, -0 vs +0, -inf) resolve in the reference's cat order: old
