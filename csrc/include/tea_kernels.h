@@ -747,3 +747,44 @@ int launch_corrcoef_merge(double* state, const double* other, int64_t tasks, hip
 // out[task] <- the value of state[6, tasks]; one launch
 int launch_corrcoef_value(const double* state, int64_t tasks, int concordance, float* out, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K17: segmentation mean IoU and Dice (csrc/kernels/segmentation.hip).  One pass over [n, c, p]
+// scores (class axis strided) or over a pair of label maps folds every counted pixel into three
+// per-class counts: intersection, predicted and target (docs/parity.md, "Not in the reference").
+// kSegMaxClasses: a block holds three u32 [c] histograms in LDS, 12 KiB at the cap; a CU holds at
+// most 8 blocks of 256 threads (2048 threads), 8 * 12 KiB = 96 KiB of its 160 KiB.
+constexpr int kSegSpan = 2048;        // pixels of one image a block owns at a time
+constexpr int kSegMaxBlocks = 1024;   // the persistent grid's cap = the most partial triples
+constexpr int kSegMaxClasses = 1024;
+struct SegmentationArgs {
+  // arm 0 (plane) and 1 (element): element (n, c, p) of the f32 / f16 / bf16 scores is at
+  // n * stride_n + c * stride_c + p * stride_p (elements).  The plane arm needs stride_p == 1 and,
+  // for 16-bit scores, stride_c % 8 == 0.  Arm 2 (label): `input` is a contiguous [n, p] integer map
+  const void* input = nullptr;
+  DType in_dt = DType::f32;
+  int64_t stride_n = 0, stride_c = 0, stride_p = 1;
+  const void* target = nullptr;  // [n, p] u8 / i8 / i16 / i32 / i64, contiguous
+  DType tg_dt = DType::i64;
+  int64_t n = 0;
+  int64_t p = 0;                 // pixels per image
+  int c = 0;                     // 1 .. kSegMaxClasses
+  int arm = 0;
+  int has_ignore = 0;
+  int64_t ignore_index = 0;
+  int* err = nullptr;            // bit 0: counted target outside [0, c); bit 1: such a label-map prediction
+  uint32_t* partial = nullptr;   // [segmentation_blocks(n, p), 3, c] scratch: intersection, pred, target
+  // the finish launch: dst[s][k] (+)= the partials of state s added in block order; `accumulate` 0
+  // overwrites (the functional's scratch triple).  With `out`, the same launch evaluates the value
+  double* dst[3] = {nullptr, nullptr, nullptr};
+  int accumulate = 0;
+  int dice = 0;                  // 0: IoU, 1: Dice
+  int average = 0;               // 0: macro, 1: micro, 2: none ([c] values)
+  float* out = nullptr;
+};
+int segmentation_blocks(int64_t n, int64_t p);  // grid of the count launch = number of partial triples
+int launch_segmentation(const SegmentationArgs& a, hipStream_t stream);
+// the value of three [c] float64 states (c >= 1, any size), by one wave
+int launch_segmentation_value(const double* intersection, const double* pred_count, const double* target_count,
+                              int64_t c, int dice, int average, float* out, hipStream_t stream);
+}  // namespace tea

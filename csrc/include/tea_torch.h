@@ -126,6 +126,7 @@ enum class Scratch : int {
   kRankCorrPartials = 16,   // K14
   kCalibrationPartials = 17,  // K15
   kCorrcoefPartials = 18,   // K16
+  kSegmentationPartials = 19,  // K17
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

@@ -72,7 +72,8 @@ PAGES: Dict[str, Tuple[str, str, List[str]]] = {
 
 
 def package_symbols(name: str) -> Tuple[str, List[str]]:
-    """(section title, public names in __all__ order) of one package."""
+    """(section title, public names in __all__ order) of one package, then its ``__doc_extras__``:
+    names a package exports without listing them in an ``__all__`` that mirrors the reference."""
     mod = importlib.import_module(name)
     title = getattr(mod, "__doc_name__", None) or name.rsplit(".", 1)[-1].replace("_", " ").title()
     names = list(getattr(mod, "__all__", []))
@@ -81,7 +82,7 @@ def package_symbols(name: str) -> Tuple[str, List[str]]:
             n for n, o in vars(mod).items()
             if not n.startswith("_") and (inspect.isfunction(o) or inspect.isclass(o)) and o.__module__ == name
         )
-    return title, names
+    return title, names + list(getattr(mod, "__doc_extras__", []))
 
 
 def render_rst(page: str) -> str:

@@ -25,6 +25,7 @@ from torcheval_amd.metrics.classification.confusion_matrix import (
     MulticlassConfusionMatrix,
 )
 from torcheval_amd.metrics.classification.f1_score import BinaryF1Score, MulticlassF1Score
+from torcheval_amd.metrics.classification.mean_iou import DiceScore, MeanIoU  # noqa: F401  (not reference names either)
 from torcheval_amd.metrics.classification.precision import BinaryPrecision, MulticlassPrecision
 from torcheval_amd.metrics.classification.precision_recall_curve import (
     BinaryPrecisionRecallCurve,
@@ -71,3 +72,4 @@ __all__ = [
     "TopKMultilabelAccuracy",
 ]
 __doc_name__ = "Classification Metrics"
+__doc_extras__ = ["DiceScore", "MeanIoU"]  # documented, not reference names

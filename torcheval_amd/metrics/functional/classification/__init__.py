@@ -39,6 +39,7 @@ from torcheval_amd.metrics.functional.classification.f1_score import (
     binary_f1_score,
     multiclass_f1_score,
 )
+from torcheval_amd.metrics.functional.classification.mean_iou import dice_score, mean_iou  # noqa: F401  (likewise)
 from torcheval_amd.metrics.functional.classification.precision import (
     binary_precision,
     multiclass_precision,
@@ -88,3 +89,4 @@ __all__ = [
     "topk_multilabel_accuracy",
 ]
 __doc_name__ = "Classification Metrics"
+__doc_extras__ = ["dice_score", "mean_iou"]  # documented, not reference names
