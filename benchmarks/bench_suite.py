@@ -268,6 +268,16 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.multiclass_calibration_error(x, t, from_logits=True)
         return make
 
+    def kl(cls):
+        def make():
+            x = torch.randn(B, C, device=dev) * 3
+            t = x + torch.randn(B, C, device=dev)
+            if cls:
+                m = M.KLDivergence(device=dev)
+                return lambda: m.update(x, t)
+            return lambda: F.kl_divergence(x, t)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -421,6 +431,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "PearsonCorrCoef.update 8192x1000 .t() (K16)": pearson(True),
         "multiclass_calibration_error logits 8192x1000 (K15)": calibration(False),
         "MulticlassCalibrationError.update logits 8192x1000 (K15)": calibration(True),
+        "kl_divergence logits 8192x1000 (K18)": kl(False),
+        "KLDivergence.update logits 8192x1000 (K18)": kl(True),
         "Sum.update 8192x1000 (K5b)": k5b(M.Sum, "sum"),
         "Mean.update 8192x1000 (K5b)": k5b(M.Mean, "sum"),
         "PeakSignalNoiseRatio.update 8192x1000 (K5b)": k5b(M.PeakSignalNoiseRatio, "psnr"),

@@ -788,3 +788,34 @@ int launch_segmentation(const SegmentationArgs& a, hipStream_t stream);
 int launch_segmentation_value(const double* intersection, const double* pred_count, const double* target_count,
                               int64_t c, int dice, int average, float* out, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K18: KL divergence KL(P || Q) of corresponding rows of two [n, c] tensors (csrc/kernels/
+// kl_divergence.hip; docs/parity.md, "Not in the reference").  P comes from `target`, Q from
+// `input`: their softmaxes (from_logits) or the rows divided by their sums.  One wave streams both
+// rows of a counted row pair once and lane 0 forms the row value in FP64.
+constexpr int kKlMaxBlocks = 1024;  // grid cap of the row launch in 4-wave blocks; rows past it grid-stride
+struct KlDivArgs {
+  // Both operands have one dtype (f32 / bf16 / f16), unit stride along c and element-aligned rows;
+  // row r of `input` and row r of `target` lie at the same offset from a 16-B boundary.
+  const void* input = nullptr;
+  const void* target = nullptr;
+  DType dt = DType::f32;
+  int64_t in_row_stride = 0, tg_row_stride = 0;  // elements
+  const uint8_t* mask = nullptr;  // optional [n] bool: a row with 0 is never read and not counted
+  int64_t n = 0;
+  int64_t c = 0;                  // 1 .. 2^31 - 1
+  int from_logits = 0;
+  float* rows_out = nullptr;      // optional [n]: the row values, 0 for uncounted rows
+  // optional [2, kl_divergence_blocks(n)] scratch: per block the FP64 sum of its row values, then
+  // its count of rows.  With it the finish launch adds the partials in block order and either
+  // accumulates into *dst_sum and *dst_count (class states) or writes *out = sum (mean: / count)
+  double* partial = nullptr;
+  double* dst_sum = nullptr;
+  double* dst_count = nullptr;
+  float* out = nullptr;
+  int mean = 0;
+};
+int kl_divergence_blocks(int64_t n);  // grid of the row launch = number of partial pairs
+int launch_kl_divergence(const KlDivArgs& a, hipStream_t stream);
+}  // namespace tea

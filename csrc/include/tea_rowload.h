@@ -1,5 +1,5 @@
 // Operand loaders of the streaming kernels whose score dtype is a template parameter (K1, K2, K7,
-// K10, K13, K15, K16), and the float helpers those kernels share.  Device code only.
+// K10, K13, K15, K16, K18), and the float helpers those kernels share.  Device code only.
 //
 // KIND: 0 = f32, 1 = bf16, 2 = f16.  The host side of every unit maps DType::f32 / bf16 / f16 to
 // <0> / <1> / <2> by the same rule.  (Operands whose dtype is only known at run time go through
@@ -91,5 +91,21 @@ __device__ __forceinline__ float finite_or_zero(float mx) { return mx == -__buil
 
 // NaN-propagating maximum (v_maximum3_f32), where fmaxf lets a NaN lose to a number
 __device__ __forceinline__ float fmaximum(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float fminimum(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+
+// e^x to about an ulp for x <= 0 (NaN stays NaN): v_exp_f32 of x * log2(e) with the product's
+// rounding error and the constant's put back to first order.  The argument is first raised to -200
+// by a NaN-propagating maximum: e^-200 is 0 in float32 as is everything below it, and from -inf or
+// a finite x near -FLT_MAX the product would overflow to -inf and the error term to +inf, 0 * inf.
+// The plain fast form loses |x| * 2^-24 relative to this one, which shows at the tolerance the
+// tests of K15 and K18 hold.
+__device__ __forceinline__ float exp_neg(float x) {
+  constexpr float kL2e = 1.44269502162933349609375f, kL2eLo = 1.92596299112661746e-8f, kLn2 = 0.693147182464599609375f;
+  x = fmaximum(x, -200.f);
+  const float t = x * kL2e;
+  const float lost = __builtin_fmaf(x, kL2e, -t) + x * kL2eLo;
+  const float e = __builtin_amdgcn_exp2f(t);  // 2^-288.5 and below: 0
+  return __builtin_fmaf(e, lost * kLn2, e);
+}
 
 }  // namespace tea

@@ -127,6 +127,7 @@ enum class Scratch : int {
   kCalibrationPartials = 17,  // K15
   kCorrcoefPartials = 18,   // K16
   kSegmentationPartials = 19,  // K17
+  kKlDivPartials = 20,      // K18
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

@@ -32,16 +32,8 @@ constexpr int kWpb = kB / kWave;
 constexpr int kFinishThreads = 1024;
 constexpr int kNoIndex = 0x7fffffff;
 
-// e^x to about an ulp for x <= 0 (x = -inf gives 0, NaN stays NaN): v_exp_f32 of x * log2(e) with
-// the product's rounding error and the constant's put back to first order.  The plain fast form
-// loses |x| * 2^-24 relative to it, which shows in the confidence at the tolerance the tests hold.
-__device__ __forceinline__ float exp_neg(float x) {
-  constexpr float kL2e = 1.44269502162933349609375f, kL2eLo = 1.92596299112661746e-8f, kLn2 = 0.693147182464599609375f;
-  const float t = x * kL2e;
-  const float lost = __builtin_fmaf(x, kL2e, -t) + x * kL2eLo;
-  const float e = __builtin_amdgcn_exp2f(t);
-  return x == -__builtin_huge_valf() ? 0.f : __builtin_fmaf(e, lost * kLn2, e);
-}
+// exp_neg (tea_rowload.h): e^x to about an ulp for x <= 0.  The plain fast form loses
+// |x| * 2^-24 relative to it, which shows in the confidence at the tolerance the tests hold.
 
 // What a lane (or the thread that owns a row) knows of the columns it has seen, which it meets in
 // ascending order: their maximum (NaN once it met one), the first column holding it, and for

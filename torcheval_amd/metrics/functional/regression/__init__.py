@@ -1,6 +1,7 @@
 """Regression metrics, functional API (parity: functional/regression/*.py)."""
 
 from torcheval_amd.metrics.functional.regression._common import _native, _update
+from torcheval_amd.metrics.functional.regression.kl_divergence import kl_divergence
 from torcheval_amd.metrics.functional.regression.mean_squared_error import (
     mean_squared_error,
     _mean_squared_error_update,
@@ -26,3 +27,4 @@ __all__ = [
     "spearman_corrcoef",
 ]
 __doc_name__ = "Regression Metrics"
+__doc_extras__ = ["kl_divergence"]  # documented, not a reference name

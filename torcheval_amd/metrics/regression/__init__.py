@@ -1,5 +1,6 @@
 """Regression class metrics (parity: metrics/regression/*.py)."""
 
+from torcheval_amd.metrics.regression.kl_divergence import KLDivergence
 from torcheval_amd.metrics.regression.mean_squared_error import MeanSquaredError
 from torcheval_amd.metrics.regression.pearson import ConcordanceCorrCoef, PearsonCorrCoef
 from torcheval_amd.metrics.regression.r2_score import R2Score
@@ -13,3 +14,4 @@ __all__ = [
     "SpearmanCorrCoef",
 ]
 __doc_name__ = "Regression Metrics"
+__doc_extras__ = ["KLDivergence"]  # documented, not a reference name
