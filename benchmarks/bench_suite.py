@@ -250,6 +250,17 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.spearman_corrcoef(x, y)
         return make
 
+    def kendall(cls, levels=None):
+        def make():
+            x, y = rand(N1M), rand(N1M)
+            if levels is not None:
+                x, y = torch.floor(x * levels), torch.floor(y * levels)
+            if cls:
+                m = M.KendallRankCorrCoef(device=dev).update(x, y)
+                return lambda: m.compute()
+            return lambda: F.kendall_rank_corrcoef(x, y)
+        return make
+
     def pearson(cls):
         def make():
             x, y = rand(B, C).t(), rand(B, C).t()  # [outputs, n] views of [n, outputs] predictions
@@ -427,6 +438,10 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "r2_score 8192x1000": r2,
         "spearman_corrcoef N=1M (K3a + K14)": spearman(False),
         "SpearmanCorrCoef.compute N=1M (K3a + K14)": spearman(True),
+        "kendall_rank_corrcoef N=1M (2 x K3a + K19)": kendall(False),
+        "KendallRankCorrCoef.compute N=1M (2 x K3a + K19)": kendall(True),
+        "kendall_rank_corrcoef N=1M, 50-level ties (2 x K3a + K19)": kendall(False, 50),
+        "KendallRankCorrCoef.compute N=1M, 50-level ties (2 x K3a + K19)": kendall(True, 50),
         "pearson_corrcoef 8192x1000 .t() (K16)": pearson(False),
         "PearsonCorrCoef.update 8192x1000 .t() (K16)": pearson(True),
         "multiclass_calibration_error logits 8192x1000 (K15)": calibration(False),

@@ -819,3 +819,40 @@ struct KlDivArgs {
 int kl_divergence_blocks(int64_t n);  // grid of the row launch = number of partial pairs
 int launch_kl_divergence(const KlDivArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K19: Kendall rank correlation per row (csrc/kernels/kendall.hip; docs/parity.md, "Not in the
+// reference").  K3a sorts `target` (payload_kind 0), kendall_prepare turns the sorted rows into the
+// tie-run starts `s` and the gathered `input`, K3a sorts that with `s` as its payload
+// (payload_kind 2), and kendall_count counts ties and the strict inversions of the carried `s`.
+constexpr int kKendallTile = 2048;  // positions a block resolves, sorts or merges in LDS
+struct KendallPrepareArgs {
+  const float* sorted = nullptr;   // [rows, n] target, sorted descending, contiguous
+  const int32_t* order = nullptr;  // [rows, n] source index of each sorted position
+  const float* x = nullptr;        // [rows, n] input in source order, contiguous
+  int64_t rows = 0;
+  int64_t n = 0;                   // 2 .. 2^31 - 1
+  int32_t* s = nullptr;            // [rows, n] start of the target tie run of each sorted position
+  float* xg = nullptr;             // [rows, n] x[order]
+  int64_t* part = nullptr;         // [rows, 6, kendall_tiles(n)]: writes planes 1 (n2) and 5 (my)
+  int32_t* flags = nullptr;        // [rows, 2]: writes [row][0] = target holds NaN | 2 * sort fault
+  const uint32_t* sort_fault = nullptr;  // K3a's onesweep timeout word of the target sort, or null
+};
+struct KendallCountArgs {
+  const float* sorted = nullptr;    // [rows, n] gathered input, sorted descending (stable), contiguous
+  const int32_t* carried = nullptr; // [rows, n] the `s` that sort carried
+  int64_t rows = 0;
+  int64_t n = 0;
+  int64_t* part = nullptr;          // [rows, 6, kendall_tiles(n)] partials of n1, n2, n3, Q, mx, my
+  int32_t* flags = nullptr;         // [rows, 2]: writes [row][1] = input holds NaN
+  int32_t* buf0 = nullptr;          // 2 x [rows, n] scratch: the merge levels' ping-pong rows
+  int32_t* buf1 = nullptr;
+  const uint32_t* sort_fault = nullptr;  // the timeout word of the input sort, or null
+  int variant = 0;                  // 0: tau-b, 1: tau-c
+  float* out = nullptr;             // [rows]
+  int64_t* counts = nullptr;        // [rows, 6]: n1, n2, n3, Q, mx, my; -1 for a task without a value
+};
+int64_t kendall_tiles(int64_t n);
+int launch_kendall_prepare(const KendallPrepareArgs& a, hipStream_t stream);
+int launch_kendall_count(const KendallCountArgs& a, hipStream_t stream);
+}  // namespace tea

@@ -23,6 +23,7 @@ from torcheval_amd.metrics.regression import MeanSquaredError, R2Score
 from torcheval_amd.metrics.regression import SpearmanCorrCoef  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.regression import ConcordanceCorrCoef, PearsonCorrCoef  # likewise
 from torcheval_amd.metrics.regression import KLDivergence  # likewise
+from torcheval_amd.metrics.regression import KendallRankCorrCoef  # likewise
 from torcheval_amd.metrics.text import (
     BLEUScore,
     Perplexity,

@@ -21,6 +21,7 @@ from torcheval_amd.metrics.functional.regression import mean_squared_error, r2_s
 from torcheval_amd.metrics.functional.regression import spearman_corrcoef  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.functional.regression import concordance_corrcoef, pearson_corrcoef  # likewise
 from torcheval_amd.metrics.functional.regression import kl_divergence  # likewise
+from torcheval_amd.metrics.functional.regression import kendall_rank_corrcoef  # likewise
 from torcheval_amd.metrics.functional.text import (
     bleu_score,
     perplexity,

@@ -1,6 +1,7 @@
 """Regression metrics, functional API (parity: functional/regression/*.py)."""
 
 from torcheval_amd.metrics.functional.regression._common import _native, _update
+from torcheval_amd.metrics.functional.regression.kendall import kendall_rank_corrcoef
 from torcheval_amd.metrics.functional.regression.kl_divergence import kl_divergence
 from torcheval_amd.metrics.functional.regression.mean_squared_error import (
     mean_squared_error,
@@ -21,6 +22,7 @@ from torcheval_amd.metrics.functional.regression.spearman import spearman_corrco
 
 __all__ = [
     "concordance_corrcoef",
+    "kendall_rank_corrcoef",
     "mean_squared_error",
     "pearson_corrcoef",
     "r2_score",

@@ -1,5 +1,6 @@
 """Regression class metrics (parity: metrics/regression/*.py)."""
 
+from torcheval_amd.metrics.regression.kendall import KendallRankCorrCoef
 from torcheval_amd.metrics.regression.kl_divergence import KLDivergence
 from torcheval_amd.metrics.regression.mean_squared_error import MeanSquaredError
 from torcheval_amd.metrics.regression.pearson import ConcordanceCorrCoef, PearsonCorrCoef
@@ -8,6 +9,7 @@ from torcheval_amd.metrics.regression.spearman import SpearmanCorrCoef
 
 __all__ = [
     "ConcordanceCorrCoef",
+    "KendallRankCorrCoef",
     "MeanSquaredError",
     "PearsonCorrCoef",
     "R2Score",
