@@ -232,6 +232,18 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.structural_similarity(x, t)
         return make
 
+    def kid(cls, rows, d):
+        def make():
+            rows_, m = (rows, 1000) if s >= 1 else (n(rows // 40), n(25))
+            real, fake = rand(rows_, d), 0.8 * rand(rows_, d) + 0.3
+            if cls:
+                metric = M.KernelInceptionDistance(model=torch.nn.Identity(), feature_dim=d, subset_size=m, seed=0,
+                                                   device=dev)
+                metric.update_activations(real, True).update_activations(fake, False)
+                return lambda: metric.compute()
+            return lambda: F.kernel_inception_distance(real, fake, subset_size=m)
+        return make
+
     def ndcg(cls):
         def make():
             x, t = rand(B, C), randint(5, B, C)
@@ -453,6 +465,9 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "PeakSignalNoiseRatio.update 8192x1000 (K5b)": k5b(M.PeakSignalNoiseRatio, "psnr"),
         "structural_similarity 64x3x256x256 (K12)": ssim(False),
         "StructuralSimilarity.update 64x3x256x256 (K12)": ssim(True),
+        "kernel_inception_distance 10000x2048, 100 subsets of 1000 (K20)": kid(False, 10000, 2048),
+        "KernelInceptionDistance.compute 10000x2048, 100 subsets of 1000 (K20)": kid(True, 10000, 2048),
+        "kernel_inception_distance 10000x64, 100 subsets of 1000 (K20)": kid(False, 10000, 64),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),
         "WeightedCalibration(64 tasks).update 8192x1000 (K5b)": k5b(M.WeightedCalibration, "wc"),
         "WindowedClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.WindowedClickThroughRate, "ctr"),

@@ -856,3 +856,40 @@ int64_t kendall_tiles(int64_t n);
 int launch_kendall_prepare(const KendallPrepareArgs& a, hipStream_t stream);
 int launch_kendall_count(const KendallCountArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K20: Kernel Inception Distance (csrc/kernels/kid.hip; docs/parity.md, "Not in the reference").
+// kid_gram_kernel forms, per subset, the three sums of the polynomial kernel over XX, YY and XY
+// straight from FP32-MFMA Gram tiles of index-gathered rows (no Gram matrix and no gathered copy
+// ever exists); kid_finish_kernel adds the tile partials, forms mmd2 per subset and its mean and
+// population standard deviation.
+constexpr int kKidTile = 128;  // rows and columns of one Gram tile
+struct KidGramArgs {
+  const float* real = nullptr;     // [n_r, D], unit stride along D
+  const float* fake = nullptr;     // [n_f, D]
+  int64_t real_stride = 0;         // row strides in elements
+  int64_t fake_stride = 0;
+  int64_t n_r = 0;
+  int64_t n_f = 0;
+  int64_t d = 0;                   // >= 1
+  const int32_t* idx_r = nullptr;  // [subsets, m] rows of `real`, contiguous; clamped to [0, n_r)
+  const int32_t* idx_f = nullptr;  // [subsets, m] rows of `fake`
+  int64_t subsets = 0;             // >= 1
+  int64_t m = 0;                   // >= 2
+  double gamma = 0.0;
+  double coef = 0.0;
+  int degree = 1;                  // 1 .. 16
+  double* partials = nullptr;      // [subsets, kid_items(m)]
+};
+struct KidFinishArgs {
+  const double* partials = nullptr;  // [subsets, kid_items(m)]
+  int64_t subsets = 0;
+  int64_t m = 0;
+  double* sums = nullptr;            // [subsets, 3]: sxx, syy, sxy
+  double* values = nullptr;          // [subsets]: mmd2
+  float* out = nullptr;              // [2]: mean and population standard deviation of `values`
+};
+int64_t kid_items(int64_t m);  // tiles per subset: T (T + 1) / 2 of XX, as many of YY, T^2 of XY
+int launch_kid_gram(const KidGramArgs& a, hipStream_t stream);
+int launch_kid_finish(const KidFinishArgs& a, hipStream_t stream);
+}  // namespace tea

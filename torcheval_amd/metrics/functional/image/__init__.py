@@ -1,5 +1,6 @@
 """Image metrics, functional API (parity: functional/image/psnr.py)."""
 
+from torcheval_amd.metrics.functional.image.kid import kernel_inception_distance
 from torcheval_amd.metrics.functional.image.psnr import (
     peak_signal_noise_ratio,
     _psnr_param_check,
@@ -10,6 +11,7 @@ from torcheval_amd.metrics.functional.image.psnr import (
 from torcheval_amd.metrics.functional.image.ssim import structural_similarity
 
 __all__ = [
+    "kernel_inception_distance",
     "peak_signal_noise_ratio",
     "structural_similarity",
 ]
