@@ -18,10 +18,11 @@ using namespace tea_torch;
 // outs[k] receives stat codes[k] / 8 with op codes[k] % 4 (see tea::RowStat / tea::RowOp), bit 2
 // of the code = row 0 only (a scalar state): f32 / f64 tensors of `rows` elements (any stride:
 // a ring-buffer column works), or of one element for row-0-only outputs.  CUDA tensors
-// run K5b (one launch, two for rows > 64K elements); CPU tensors the host twin.
+// run K5b (one launch, two for rows > 32768 elements); CPU tensors the host twin.
 static tea::RowSumsArgs row_sums_args(const Tensor& x_in, const optional<Tensor>& t_in, const optional<Tensor>& w_in,
                                       double w_scalar, const std::vector<Tensor>& outs,
-                                      const std::vector<int64_t>& codes, int64_t rows, Tensor* x_out) {
+                                      const std::vector<int64_t>& codes, int64_t rows, Tensor* x_out,
+                                      bool reads_inputs = true) {
   // any shape: a [rows, n] view is used as is, anything else is viewed as rows x (numel / rows)
   auto as_rows = [&](const Tensor& v) -> Tensor {
     if (v.dim() == 2 && v.size(0) == rows) return v;
@@ -68,6 +69,13 @@ static tea::RowSumsArgs row_sums_args(const Tensor& x_in, const optional<Tensor>
     if (a.out[k].stat < tea::kCOUNT) need |= 1 << a.out[k].stat;
     if (a.out[k].stat == tea::kRANGE) need |= (1 << tea::kTMIN) | (1 << tea::kTMAX);
   }
+  // WT, SSE, WSSE, WTT, TMIN, TMAX (and RANGE through the last two) read the target: without one
+  // the kernel would load through a null pointer and the host twin would take t as 0 (the fold of
+  // pending slots reads no input at all)
+  constexpr int need_t = (1 << tea::kWT) | (1 << tea::kSSE) | (1 << tea::kWSSE) | (1 << tea::kWTT) |
+                         (1 << tea::kTMIN) | (1 << tea::kTMAX);
+  TORCH_CHECK(!reads_inputs || t.has_value() || (need & need_t) == 0,
+              "row_sums: a statistic that reads the target needs t");
   a.need = need;
   *x_out = x;
   return a;
@@ -139,7 +147,7 @@ void row_sums_fold(const Tensor& pend, int64_t used, const std::vector<Tensor>& 
   TORCH_CHECK(!outs.empty(), "row_sums_fold: no outputs");
   const Tensor carrier = at::empty({rows, 0}, pend.options().dtype(at::kFloat));
   Tensor x;
-  tea::RowSumsArgs a = row_sums_args(carrier, c10::nullopt, c10::nullopt, 1.0, outs, codes, rows, &x);
+  tea::RowSumsArgs a = row_sums_args(carrier, c10::nullopt, c10::nullopt, 1.0, outs, codes, rows, &x, false);
   TORCH_CHECK(pend.scalar_type() == at::kDouble && pend.is_cuda() &&
                   pend.numel() >= a.rows * tea::kRowPendStats * tea::kRowPendBlocks,
               "row_sums_fold: bad pend buffer");

@@ -121,6 +121,8 @@ template <int NEED, bool HAS_W, bool VEC, int BS = kB, int VPT = kVecPerThread>
 __device__ Acc reduce_range(const RowSumsArgs& g, int64_t r, int64_t lo, int64_t hi) {
   constexpr int64_t kChunk = static_cast<int64_t>(BS) * VPT * 4;
   constexpr bool HAS_T = (NEED & kNeedT) != 0;
+  // the generic instantiation also serves sets that read no target ({W}, {COUNT}), called without one
+  const bool has_t = HAS_T && (NEED != kAll || g.t != nullptr);
   Acc a;
   acc_init(a);
   const int need = g.need;
@@ -140,7 +142,7 @@ __device__ Acc reduce_range(const RowSumsArgs& g, int64_t r, int64_t lo, int64_t
       }
     };
     const float* xr = static_cast<const float*>(g.x) + r * g.x_rs;
-    const float* tr = HAS_T ? static_cast<const float*>(g.t) + r * g.t_rs : nullptr;
+    const float* tr = has_t ? static_cast<const float*>(g.t) + r * g.t_rs : nullptr;
     const float* wr = HAS_W ? static_cast<const float*>(g.w) + r * g.w_rs : nullptr;
     // 16-B loads at any 4-B alignment: the body is every whole group of 4 from lo
     const int64_t vlo = lo, vhi = lo + (hi - lo) / 4 * 4;
@@ -156,7 +158,7 @@ __device__ Acc reduce_range(const RowSumsArgs& g, int64_t r, int64_t lo, int64_t
         const int64_t i = base + 4 * (static_cast<int64_t>(u) * BS + threadIdx.x);
         const int64_t ic = i < vhi ? i : vlo;
         xv[u] = load_f4u(xr + ic);  // 4-B alignment suffices (tea_common.h)
-        tv[u] = HAS_T ? load_f4u(tr + ic) : z;
+        tv[u] = has_t ? load_f4u(tr + ic) : z;
         wv[u] = HAS_W ? load_f4u(wr + ic) : z;
       }
       if (base + kChunk <= vhi) {  // whole chunk in range (block-uniform): no per-lane branch
@@ -201,13 +203,13 @@ __device__ Acc reduce_range(const RowSumsArgs& g, int64_t r, int64_t lo, int64_t
     }
     // ragged head / tail (< 4 elements each side)
     for (int64_t i = lo + threadIdx.x; i < min(vlo, hi); i += BS)
-      acc_elem<NEED, HAS_W>(a, need, xr[i], HAS_T ? tr[i] : 0.f, HAS_W ? wr[i] : 0.f);
+      acc_elem<NEED, HAS_W>(a, need, xr[i], has_t ? tr[i] : 0.f, HAS_W ? wr[i] : 0.f);
     for (int64_t i = max(vhi, vlo) + threadIdx.x; i < hi; i += BS)
-      acc_elem<NEED, HAS_W>(a, need, xr[i], HAS_T ? tr[i] : 0.f, HAS_W ? wr[i] : 0.f);
+      acc_elem<NEED, HAS_W>(a, need, xr[i], has_t ? tr[i] : 0.f, HAS_W ? wr[i] : 0.f);
   } else {
     for (int64_t i = lo + threadIdx.x; i < hi; i += BS) {
       const double x = load_as_f64(g.x, g.x_dt, r * g.x_rs + i * g.x_cs);
-      const double t = HAS_T ? load_as_f64(g.t, g.t_dt, r * g.t_rs + i * g.t_cs) : 0.0;
+      const double t = has_t ? load_as_f64(g.t, g.t_dt, r * g.t_rs + i * g.t_cs) : 0.0;
       const double w = HAS_W ? load_as_f64(g.w, g.w_dt, r * g.w_rs + i * g.w_cs) : 0.0;
       acc_elem<NEED, HAS_W>(a, need, x, t, w);
     }

@@ -21,7 +21,7 @@ stat        value per row                          typical state
 
 ops: ``SET`` (=), ``ADD`` (+=), ``MIN``, ``MAX`` - each in the output's own dtype (f32/f64),
 exactly like ``state = state op value``.  ROCm tensors: one kernel launch (two for rows longer
-than 64K elements); CPU tensors up to ``HOST_MAX`` elements: the C++ host twin (one call
+than 32768 elements); CPU tensors up to ``HOST_MAX`` elements: the C++ host twin (one call
 instead of 4-6 ATen dispatches); larger CPU tensors keep the ATen path.
 """
 
