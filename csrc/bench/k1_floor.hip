@@ -9,6 +9,16 @@
 //          store per wave only when an impossible value appears (keeps the loads live)
 //   empty  the same 2048 x 256 grid, no work
 //   (+ the read floor behind the wide argument struct, with one atomic, with prod's row reduction)
+//   read / prod, preloaded   the same two launches from this file's second compile, in which the
+//          kernels' plain parameters are preloaded into SGPRs (as torcheval_amd/ops/build.py
+//          compiles classification.hip); in the first compile the same kernels fetch them
+//          with scalar loads at the head of every wave
+//
+// Two objects from this one file (the preload flag holds for a whole translation unit):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icsrc/include -c csrc/bench/k1_floor.hip -o k1_floor.o
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icsrc/include -DK1_FLOOR_PRELOAD_UNIT \
+//         -mllvm -amdgpu-kernarg-preload-count=16 -c csrc/bench/k1_floor.hip -o k1_floor_preload.o
+//   hipcc --offload-arch=gfx950 k1_floor.o k1_floor_preload.o -o csrc/bench/k1_floor.bin
 //
 // Usage: k1_floor.bin [pool=8] [iters=400]; prints one line per variant.
 #include <hip/hip_runtime.h>
@@ -19,6 +29,11 @@
 #include <cstdlib>
 #include <vector>
 
+#ifdef K1_FLOOR_PRELOAD_UNIT  // the second copy of the production launchers gets its own names
+#define launch_cls_counts launch_cls_counts_preload
+#define launch_micro_finish launch_micro_finish_preload
+#define launch_binary_counts launch_binary_counts_preload
+#endif
 #include "../kernels/classification.hip"
 
 using namespace tea;
@@ -52,6 +67,27 @@ __global__ __launch_bounds__(256) void read_floor_kernel(const float* __restrict
   const int64_t t = y[row];
   if (m == 12345.678f && t == 7) sink[row] = m;  // never true for randn-like data
 }
+
+}  // namespace
+
+// the preloaded variants, defined by the K1_FLOOR_PRELOAD_UNIT compile of this file
+void k1_floor_read_preload(const float* x, const int64_t* y, float* sink, hipStream_t s);
+int k1_floor_prod_preload(const ClsCountsArgs& a, hipStream_t s);
+int k1_floor_finish_preload(unsigned long long* pend, float* correct, const float* total, float* out, hipStream_t s);
+
+#ifdef K1_FLOOR_PRELOAD_UNIT
+
+void k1_floor_read_preload(const float* x, const int64_t* y, float* sink, hipStream_t s) {
+  hipLaunchKernelGGL(read_floor_kernel, dim3(N / 4), dim3(256), 0, s, x, y, sink);
+}
+int k1_floor_prod_preload(const ClsCountsArgs& a, hipStream_t s) { return launch_cls_counts(a, s); }
+int k1_floor_finish_preload(unsigned long long* pend, float* correct, const float* total, float* out, hipStream_t s) {
+  return launch_micro_finish(pend, correct, total, out, s);
+}
+
+#else
+
+namespace {
 
 // the same pure-read body behind the ~200-byte ClsCountsArgs kernel-argument block
 __global__ __launch_bounds__(256) void read_floor_bigargs_kernel(ClsCountsArgs a) {
@@ -200,7 +236,7 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
 
-  auto prod = [&](int i) {
+  auto prod_args = [&](int i) {
     ClsCountsArgs a;
     a.input = xs[i % POOL];
     a.in_dt = DType::f32;
@@ -214,8 +250,11 @@ int main(int argc, char** argv) {
     a.micro_correct = correct;
     a.micro_total = total;
     a.pend = pend;
-    launch_cls_counts(a, 0);
+    return a;
   };
+  auto prod = [&](int i) { launch_cls_counts(prod_args(i), 0); };
+  auto prodpl = [&](int i) { k1_floor_prod_preload(prod_args(i), 0); };
+  auto readpl = [&](int i) { k1_floor_read_preload(xs[i % POOL], ys[i % POOL], sink, 0); };
   auto read = [&](int i) {
     hipLaunchKernelGGL(read_floor_kernel, dim3(N / 4), dim3(256), 0, 0, xs[i % POOL], ys[i % POOL], sink);
   };
@@ -250,7 +289,7 @@ int main(int argc, char** argv) {
   auto empty1 = [&](int) { hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, 0); };
 
   // interleave the variants over 3 rounds and keep each one's best median-of-round
-  constexpr int NV = 11;
+  constexpr int NV = 13;
   float best[NV];
   for (float& b : best) b = 1e9f;
   for (int r = 0; r < 3; ++r) {
@@ -265,23 +304,28 @@ int main(int argc, char** argv) {
     best[8] = std::min(best[8], time_it(read1024, iters, e0, e1));
     best[9] = std::min(best[9], time_it(empty1024, iters, e0, e1));
     best[10] = std::min(best[10], time_it(empty1, iters, e0, e1));
+    best[11] = std::min(best[11], time_it(readpl, iters, e0, e1));
+    best[12] = std::min(best[12], time_it(prodpl, iters, e0, e1));
   }
   const double bytes = static_cast<double>(N) * C * 4 + N * 8;
   const char* names[NV] = {"prod (launch_cls_counts micro)", "read floor (same geometry)", "empty (2048 x 256)",
                            "read floor behind ClsCountsArgs", "read floor + one atomic", "read floor + DPP max + target compare",
                            "read floor, non-temporal loads", "read floor, 512-thread workgroups",
-                           "read floor, 1024-thread workgroups", "empty (512 x 1024)", "empty (1 x 64)"};
+                           "read floor, 1024-thread workgroups", "empty (512 x 1024)", "empty (1 x 64)",
+                           "read floor, preloaded arguments", "prod, preloaded arguments"};
   for (int v = 0; v < NV; ++v)
     printf("{\"variant\": \"%s\", \"pool\": %d, \"us_per_launch\": %.3f, \"TBps\": %.2f}\n", names[v], POOL, best[v],
-           (v != 2 && v < 9) ? bytes / (best[v] * 1e-6) / 1e12 : 0.0);
+           (v != 2 && (v < 9 || v > 10)) ? bytes / (best[v] * 1e-6) / 1e12 : 0.0);
   printf("{\"prod_over_floor\": %.4f}\n", best[0] / best[1]);
+  printf("{\"prod_preloaded_over_prod\": %.4f, \"read_preloaded_over_read\": %.4f}\n", best[12] / best[0],
+         best[11] / best[1]);
 
   // Host side: the host cost of one production launch with no Python in
   // front of it, and bench.py's timed region (synchronize, t0, 20 updates, the micro_finish
   // fold, synchronize, t1) driven from C++: what the region costs with a zero-overhead caller.
   float* acc_out;
   CK(hipMalloc(&acc_out, 4));
-  std::vector<double> enq, region1, region20;
+  std::vector<double> enq, region1, region20, region1pl, region20pl;
   for (int rep = 0; rep < 41; ++rep) {
     CK(hipDeviceSynchronize());
     auto t0 = std::chrono::steady_clock::now();
@@ -298,6 +342,15 @@ int main(int argc, char** argv) {
       CK(hipDeviceSynchronize());
       auto r1 = std::chrono::steady_clock::now();
       (n == 1 ? region1 : region20).push_back(std::chrono::duration<double, std::micro>(r1 - r0).count());
+      // the same region with preloaded arguments in both kernels
+      for (int i = 0; i < 5; ++i) prodpl(i);
+      CK(hipDeviceSynchronize());
+      r0 = std::chrono::steady_clock::now();
+      for (int i = 0; i < n; ++i) prodpl(i);
+      k1_floor_finish_preload(pend, correct, total, acc_out, 0);
+      CK(hipDeviceSynchronize());
+      r1 = std::chrono::steady_clock::now();
+      (n == 1 ? region1pl : region20pl).push_back(std::chrono::duration<double, std::micro>(r1 - r0).count());
     }
   }
   auto med = [](std::vector<double> v) {
@@ -307,5 +360,9 @@ int main(int argc, char** argv) {
   printf("{\"host_us_per_launch\": %.3f, \"region_1_us\": %.2f, \"region_20_us\": %.2f, "
          "\"updates_per_s_at_20\": %.0f}\n",
          med(enq), med(region1), med(region20), 20.0 / med(region20) * 1e6);
+  printf("{\"preloaded\": true, \"region_1_us\": %.2f, \"region_20_us\": %.2f, \"updates_per_s_at_20\": %.0f}\n",
+         med(region1pl), med(region20pl), 20.0 / med(region20pl) * 1e6);
   return 0;
 }
+
+#endif  // K1_FLOOR_PRELOAD_UNIT

@@ -484,30 +484,21 @@ __global__ __launch_bounds__(kBlock) void cls_micro_kernel(ClsCountsArgs a) {
   block_micro(a, correct_acc, rows_acc);
 }
 
-// The north-star launch: pending-cell epilogue and a compact kernel-argument block.  Each
-// wave's first instructions wait on its kernel arguments, and with ClsCountsArgs (~200 B) and
-// in-kernel lane-mask arithmetic the generated code issued the kernarg loads in two dependent
-// rounds and ~60 scalar instructions before the first row load.  Here everything the row
-// loads need sits in one 56-byte block (one scalar round trip) and the row test needs no lane
-// masks (profiles/k1_floor_r4*.txt).
-struct MicroPendArgs {
-  const void* input;
-  const void* target;
-  unsigned long long* pend;
-  float* total;
-  int64_t n;
-  int64_t row_stride;
-  int32_t c;
-  int32_t pad;
-};
-
+// The north-star launch: pending-cell epilogue and plain kernel parameters.  Each wave's first
+// instructions used to wait on a scalar-cache-cold load of its kernel arguments before any row
+// load could issue.  Plain pointer / integer parameters (a struct passed by value is not
+// eligible) are preloaded into SGPRs by the dispatcher when this unit is compiled with
+// -mllvm -amdgpu-kernarg-preload-count=16 (torcheval_amd/ops/build.py): 14 SGPRs, pointers first
+// in the order the row loads need them.  The grid-stride step travels as a parameter too
+// (gridDim.x is a hidden argument, which is not preloaded), so the kernel body holds no argument
+// load at all.  The row test needs no lane masks (profiles/k1_floor_r4*.txt,
+// profiles/k1_head_tail_ab.json).
 template <int KIND, typename TGT, bool UNAL>
-__device__ __forceinline__ bool micro_row(const MicroPendArgs& a, const char* __restrict__ rp, int64_t t, int lane) {
+__device__ __forceinline__ bool micro_row(int C, const char* __restrict__ rp, int64_t t, int lane) {
   constexpr int VEC = KIND == 0 ? 4 : 8;
   constexpr int NV = kChunkLoads * VEC;
   constexpr int STEP = kWave * VEC;
   typedef typename RowVals<NV>::type vec_t;
-  const int C = a.c;
   float f[kChunkLoads][VEC];
 #pragma unroll
   for (int u = 0; u < kChunkLoads; ++u) load_row_vec<KIND, VEC, UNAL>(rp, u * STEP + lane * VEC, C, f[u]);
@@ -540,30 +531,34 @@ __device__ __forceinline__ bool micro_row(const MicroPendArgs& a, const char* __
 }
 
 template <int KIND, typename TGT, int WPB, bool UNAL>
-__global__ __launch_bounds__(WPB * kWave) void cls_micro_pend_kernel(MicroPendArgs a) {
+__global__ __launch_bounds__(WPB * kWave) void cls_micro_pend_kernel(const char* __restrict__ input,
+                                                                     const TGT* __restrict__ target,
+                                                                     unsigned long long* __restrict__ pend,
+                                                                     float* __restrict__ total, int64_t n,
+                                                                     int64_t row_stride, int32_t c,
+                                                                     int32_t nwaves /* gridDim.x * WPB */) {
   const int lane = lane_id();
-  const int64_t nwaves = static_cast<int64_t>(gridDim.x) * WPB;
   // the wave's first row is loaded unconditionally (clamped to the last row), so nothing
-  // branches on `n` before the loads and every kernel argument arrives in one scalar round trip
+  // branches on `n` before the loads
   const int64_t row0 = static_cast<int64_t>(blockIdx.x) * WPB + wave_id();
-  const int64_t r0 = row0 < a.n ? row0 : a.n - 1;  // the launcher guarantees n >= 1
-  const bool c0 =
-      micro_row<KIND, TGT, UNAL>(a, static_cast<const char*>(a.input) + r0 * a.row_stride * kind_bytes<KIND>,
-                                 static_cast<const TGT*>(a.target)[r0], lane);
-  uint32_t correct_acc = (row0 < a.n && c0) ? 1u : 0u;
-  for (int64_t row = row0 + nwaves; row < a.n; row += nwaves) {
-    const char* rp = static_cast<const char*>(a.input) + row * a.row_stride * kind_bytes<KIND>;
-    correct_acc += micro_row<KIND, TGT, UNAL>(a, rp, static_cast<const TGT*>(a.target)[row], lane);
-  }
+  const int64_t r0 = row0 < n ? row0 : n - 1;  // the launcher guarantees n >= 1
+  const bool c0 = micro_row<KIND, TGT, UNAL>(c, input + r0 * row_stride * kind_bytes<KIND>, target[r0], lane);
+  uint32_t correct_acc = (row0 < n && c0) ? 1u : 0u;
+  for (int64_t row = row0 + nwaves; row < n; row += nwaves)
+    correct_acc += micro_row<KIND, TGT, UNAL>(c, input + row * row_stride * kind_bytes<KIND>, target[row], lane);
   // deferred fold: one no-return atomic per wave into one of 64 pending cells, no LDS, no
   // block barrier, no returning atomic on the kernel's tail (the fold's ~0.6 us + the block
   // reduction's ~0.45 us in the A/B harness); the metric folds the cells at compute / sync
   if (lane == 0 && correct_acc)
-    atomicAdd(a.pend + ((blockIdx.x * WPB + wave_id()) % kPendCells) * kPendStride,
+    atomicAdd(pend + ((blockIdx.x * WPB + wave_id()) % kPendCells) * kPendStride,
               static_cast<unsigned long long>(correct_acc));
-  if (blockIdx.x == 0 && threadIdx.x == 0 && a.total) atomicAdd(a.total, static_cast<float>(a.n));
+  if (blockIdx.x == 0 && threadIdx.x == 0 && total) atomicAdd(total, static_cast<float>(n));
 }
 
+// The fold of the pending cells.  Its four pointers are preloaded as well (same translation
+// unit).  A one-round-trip form (cells, correct and total loaded together ahead of the stores, a
+// 64-bit DPP sum instead of LDS shuffles) ran 1.75 us against 2.40 us under the tracer but did
+// not move the benchmark beyond its spread (profiles/k1_head_tail_ab.json), so the plain form stays.
 __global__ __launch_bounds__(kWave) void micro_finish_kernel(unsigned long long* pend, float* correct,
                                                              const float* total, float* out) {
   unsigned long long* cell = pend + threadIdx.x * kPendStride;
@@ -719,7 +714,8 @@ void launch_wide(const ClsCountsArgs& a, int grid, hipStream_t s) {
   const bool micro_only = micro_on && pred_free && VEC > 1 && a.k == 1 && a.cls_correct == nullptr &&
                           a.cls_label == nullptr && a.err == nullptr && a.err_max == nullptr && !a.check_target;
   if (micro_only && a.pend && (a.tg_dt == DType::i64 || a.tg_dt == DType::i32)) {
-    const MicroPendArgs m{a.input, a.target, a.pend, a.micro_total, a.n, a.row_stride, static_cast<int32_t>(a.c), 0};
+    const char* in = static_cast<const char*>(a.input);
+    const int32_t c = static_cast<int32_t>(a.c);
     // 512-thread workgroups (8 waves, still one wave per row, 1024 blocks): the driver command
     // 144.9k vs 142.7k updates/s with 4-wave workgroups, interleaved on one box, and the floor
     // harness 6.23 vs 6.30 us per launch (profiles/k1_wpb_ab_r4.txt).  TORCHEVAL_AMD_K1_WPB=4
@@ -731,15 +727,21 @@ void launch_wide(const ClsCountsArgs& a, int grid, hipStream_t s) {
     if (wpb == 8) {
       const int g8 = stream_grid(a.n, 8, a.max_blocks > 0 ? (a.max_blocks + 1) / 2 : 1024);
       if (a.tg_dt == DType::i64)
-        hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, m);
+        hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, in,
+                           static_cast<const int64_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c, g8 * 8);
       else
-        hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int32_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, m);
+        hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int32_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, in,
+                           static_cast<const int32_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c, g8 * 8);
       return;
     }
     if (a.tg_dt == DType::i64)
-      hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, kWavesPerBlock, UNAL>), dim3(grid), dim3(kBlock), 0, s, m);
+      hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, kWavesPerBlock, UNAL>), dim3(grid), dim3(kBlock), 0, s, in,
+                         static_cast<const int64_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c,
+                         grid * kWavesPerBlock);
     else
-      hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int32_t, kWavesPerBlock, UNAL>), dim3(grid), dim3(kBlock), 0, s, m);
+      hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int32_t, kWavesPerBlock, UNAL>), dim3(grid), dim3(kBlock), 0, s, in,
+                         static_cast<const int32_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c,
+                         grid * kWavesPerBlock);
     return;
   }
   if (micro_only && a.tg_dt == DType::i64) {

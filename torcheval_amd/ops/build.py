@@ -86,10 +86,18 @@ def _flags(kind: str) -> List[str]:
     return base
 
 
+# Extra flags of single translation units, by file name.  classification.hip: the K1 micro
+# update and fold kernels take plain pointer / integer parameters, which the dispatcher preloads
+# into SGPRs under this flag (kernels whose arguments are one struct by value are not affected).
+FILE_FLAGS = {
+    "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
+}
+
+
 def _compile(src: str, kind: str, hdr: str, force: bool, verbose: bool) -> str:
     os.makedirs(BUILD, exist_ok=True)
     obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-    cmd = _flags(kind) + ["-c", src, "-o", obj]
+    cmd = _flags(kind) + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     with open(src, "rb") as fh:
         digest = hashlib.sha256(fh.read() + hdr.encode() + " ".join(cmd).encode()).hexdigest()
     stamp = obj + ".sha"
