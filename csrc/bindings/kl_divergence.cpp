@@ -53,7 +53,7 @@ tea::KlDivArgs kl_args(const Tensor& input, const Tensor& target, const optional
   a.dt = dt_of(input);
   a.c = c;
   a.from_logits = from_logits ? 1 : 0;
-  const int els = st == at::kFloat ? 4 : 2;
+  const int els = tea::dtype_bytes(a.dt);
   const uintptr_t xi = reinterpret_cast<uintptr_t>(a.input), ti = reinterpret_cast<uintptr_t>(a.target);
   TORCH_CHECK(xi % els == 0 && ti % els == 0 && (xi - ti) % 16 == 0 &&
                   (a.n <= 1 || ((a.in_row_stride - a.tg_row_stride) * els) % 16 == 0),

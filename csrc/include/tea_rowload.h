@@ -2,7 +2,7 @@
 // K10, K13, K15, K16, K18), and the float helpers those kernels share.  Device code only.
 //
 // KIND: 0 = f32, 1 = bf16, 2 = f16.  The host side of every unit maps DType::f32 / bf16 / f16 to
-// <0> / <1> / <2> by the same rule.  (Operands whose dtype is only known at run time go through
+// <0> / <1> / <2> through with_kind of tea_types.h (K1 alone keeps its own table).  (Operands whose dtype is only known at run time go through
 // load_as_f32 / f64 / i64 of tea_common.h instead.)
 #pragma once
 

@@ -557,14 +557,6 @@ int dense_chunk(int T, int64_t c) {
 bool dense_eligible(int T, int64_t c) {
   return (T + 1) * c >= 256 && dense_chunk(T, c) >= 1;
 }
-int dtype_bytes(DType d) {
-  switch (d) {
-    case DType::f64: case DType::i64: return 8;
-    case DType::f32: case DType::i32: return 4;
-    case DType::f16: case DType::bf16: case DType::i16: return 2;
-    default: return 1;
-  }
-}
 }  // namespace
 
 int64_t binned_workspace_words(int T, int64_t c) { return static_cast<int64_t>(kReplicas) * (T + 1) * c * 2; }

@@ -21,6 +21,7 @@
 // is counted nowhere else and sets a bit of ``err``, the only atomic.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_partials.h"
 #include "tea_rowload.h"
 
 namespace tea {
@@ -278,23 +279,7 @@ __global__ __launch_bounds__(kFinishThreads) void calibration_finish_kernel(Cali
   const int runs = kFinishThreads / pairs;  // >= 1: pairs <= 3 * kCalibMaxBins < kFinishThreads
   const int per = (blocks + runs - 1) / runs;
   const int q = threadIdx.x / pairs, p = threadIdx.x % pairs;
-  if (q < runs) {
-    double acc = 0.0;
-    const int end = min(blocks, (q + 1) * per);
-    const double* src = a.partial + p;
-    int k = q * per;
-    // 16 unconditional loads in flight (clamped to the run's last block, counted as 0 past it), then
-    // their adds in block order: a load per add waits one round trip each, 17.6 us for 1024 blocks
-    // of 15 bins against 9.5 (profiles/calibration_r11.json)
-    for (; k < end; k += 16) {
-      double v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = src[static_cast<int64_t>(min(k + i, end - 1)) * pairs];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc += k + i < end ? v[i] : 0.0;
-    }
-    run[q * pairs + p] = acc;
-  }
+  if (q < runs) run[q * pairs + p] = run_fold<double>(a.partial + p, pairs, q * per, min(blocks, (q + 1) * per));
   __syncthreads();
   if (threadIdx.x < pairs) {
     double acc = 0.0;
@@ -332,15 +317,9 @@ int launch_calibration(const CalibrationArgs& a, hipStream_t stream) {
   if (a.c < 1 || a.c > 2147483647LL || a.n_bins < 1 || a.n_bins > kCalibMaxBins || a.norm < 0 || a.norm > 2) return -1;
   if (a.partial == nullptr || a.dst[0] == nullptr || a.dst[1] == nullptr || a.dst[2] == nullptr) return -1;
   if (a.tg_dt != DType::i64 && a.tg_dt != DType::i32) return -1;
-  const int els = a.in_dt == DType::f32 ? 4 : 2;
-  if (reinterpret_cast<uintptr_t>(a.input) % els != 0) return -2;  // rows must be element-aligned
+  if (reinterpret_cast<uintptr_t>(a.input) % dtype_bytes(a.in_dt) != 0) return -2;  // rows must be element-aligned
   const int blocks = calibration_blocks(a.n, a.c);
-  switch (a.in_dt) {
-    case DType::f32: launch_rows<0>(a, blocks, stream); break;
-    case DType::bf16: launch_rows<1>(a, blocks, stream); break;
-    case DType::f16: launch_rows<2>(a, blocks, stream); break;
-    default: return -1;
-  }
+  if (with_kind(a.in_dt, [&](auto kind) { return launch_rows<kind()>(a, blocks, stream), 0; }) != 0) return -1;
   hipLaunchKernelGGL(calibration_finish_kernel, dim3(1), dim3(kFinishThreads), 0, stream, a, blocks);
   return static_cast<int>(hipGetLastError());
 }

@@ -23,6 +23,7 @@
 // its own task's m2 NaN through the arithmetic (inf - inf^2 / n) and touches no other task.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_partials.h"
 #include "tea_rowload.h"
 
 namespace tea {
@@ -146,6 +147,8 @@ __global__ __launch_bounds__(kB) void corr_row_kernel(CorrcoefArgs a, int bpt) {
   if (t < head) s.add(load1<KX>(xr, s0 + t) - px, load1<KY>(yr, s0 + t) - py);
   if (t < len - tail0) s.add(load1<KX>(xr, s0 + tail0 + t) - px, load1<KY>(yr, s0 + tail0 + t) - py);
 
+  // this block's five sums; kept here: through a shared K-value block sum the kernel's instructions
+  // move (profiles/partials_dedup_codegen.txt)
   const int lane = lane_id(), w = wave_id();
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
@@ -278,14 +281,8 @@ __global__ __launch_bounds__(kB) void corr_finish_kernel(CorrcoefArgs a, int bpt
   const int64_t task = static_cast<int64_t>(blockIdx.x) * kWpb + wave_id();
   if (task >= a.tasks) return;
   const int lane = lane_id();
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  const double* p = a.partial + task * bpt * 5;
-  for (int j = lane; j < bpt; j += kWave) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) s[k] += p[static_cast<int64_t>(j) * 5 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = wave_sum(s[k]);
+  double s[5];
+  wave_strided_sum(a.partial + task * bpt * 5, bpt, 5, 1, s);
   if (lane != 0) return;
   const double px = pivot_of(a.x, a.x_dt, task * a.x_task_stride);
   const double py = pivot_of(a.y, a.y_dt, task * a.y_task_stride);
@@ -313,20 +310,6 @@ void launch_arm(const CorrcoefArgs& a, int64_t grid, int bpt, hipStream_t s) {
   else hipLaunchKernelGGL((corr_row_kernel<KX, KY>), dim3(grid), dim3(kB), 0, s, a, bpt);
 }
 
-template <int KX>
-int launch_arm_y(const CorrcoefArgs& a, int64_t grid, int bpt, hipStream_t s) {
-  switch (a.y_dt) {
-    case DType::f32: launch_arm<KX, 0>(a, grid, bpt, s); return 0;
-    case DType::bf16: launch_arm<KX, 1>(a, grid, bpt, s); return 0;
-    case DType::f16: launch_arm<KX, 2>(a, grid, bpt, s); return 0;
-    default: return -1;
-  }
-}
-
-bool element_aligned(const void* p, DType dt) {
-  return reinterpret_cast<uintptr_t>(p) % (dt == DType::f32 ? 4 : 2) == 0;
-}
-
 }  // namespace
 
 int corrcoef_blocks(int64_t n, int column) {
@@ -337,7 +320,8 @@ int corrcoef_blocks(int64_t n, int column) {
 int launch_corrcoef(const CorrcoefArgs& a, hipStream_t stream) {
   if (a.tasks < 1 || a.n < 1 || a.n > 2147483647LL) return -1;
   if (a.x == nullptr || a.y == nullptr || a.partial == nullptr || (a.moments == nullptr && a.out == nullptr)) return -1;
-  if (!element_aligned(a.x, a.x_dt) || !element_aligned(a.y, a.y_dt)) return -2;
+  if (reinterpret_cast<uintptr_t>(a.x) % dtype_bytes(a.x_dt) != 0) return -2;
+  if (reinterpret_cast<uintptr_t>(a.y) % dtype_bytes(a.y_dt) != 0) return -2;
   if (a.column ? (a.x_task_stride != 1 || a.y_task_stride != 1) : (a.x_sample_stride != 1 || a.y_sample_stride != 1))
     return -1;
   const int bpt = corrcoef_blocks(a.n, a.column);
@@ -345,13 +329,9 @@ int launch_corrcoef(const CorrcoefArgs& a, hipStream_t stream) {
   const int64_t grid = tiles * bpt;
   const int64_t finish_grid = (a.tasks + kWpb - 1) / kWpb;
   if (grid > 2147483647LL || finish_grid > 2147483647LL) return -3;
-  int rc = -1;
-  switch (a.x_dt) {
-    case DType::f32: rc = launch_arm_y<0>(a, grid, bpt, stream); break;
-    case DType::bf16: rc = launch_arm_y<1>(a, grid, bpt, stream); break;
-    case DType::f16: rc = launch_arm_y<2>(a, grid, bpt, stream); break;
-    default: break;
-  }
+  const int rc = with_kind(a.x_dt, [&](auto kx) {
+    return with_kind(a.y_dt, [&](auto ky) { return launch_arm<decltype(kx)::value, ky()>(a, grid, bpt, stream), 0; });
+  });
   if (rc != 0) return rc;
   hipLaunchKernelGGL(corr_finish_kernel, dim3(finish_grid), dim3(kB), 0, stream, a, bpt);
   return static_cast<int>(hipGetLastError());

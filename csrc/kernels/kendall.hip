@@ -36,6 +36,7 @@
 #include <cstdint>
 
 #include "tea_kernels.h"
+#include "tea_partials.h"
 
 namespace tea {
 namespace {
@@ -402,10 +403,7 @@ __global__ __launch_bounds__(64) void kendall_finish_kernel(KendallCountArgs a, 
     for (int k = 0; k < 6; ++k) v[k] += static_cast<u64>(p[k * tiles + b]);
   }
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-  }
+  for (int k = 0; k < 6; ++k) v[k] = wave_sum(v[k]);
   if (threadIdx.x >= 6) return;
   const bool nan = a.flags[row * 2] != 0 || a.flags[row * 2 + 1] != 0 ||
                    (a.sort_fault != nullptr && *a.sort_fault != 0u);

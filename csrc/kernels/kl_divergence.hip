@@ -27,6 +27,7 @@
 // launches, no atomic, no host synchronisation, bit-identical between runs.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_partials.h"
 #include "tea_rowload.h"
 
 namespace tea {
@@ -212,17 +213,7 @@ __global__ __launch_bounds__(kFinishThreads) void kl_divergence_finish_kernel(Kl
   __shared__ double tot[2];
   const int v = threadIdx.x / kFinishRuns, q = threadIdx.x % kFinishRuns;
   const int per = (blocks + kFinishRuns - 1) / kFinishRuns;
-  const int end = min(blocks, (q + 1) * per);
-  const double* src = a.partial + static_cast<int64_t>(v) * blocks;
-  double acc = 0.0;
-  for (int k = q * per; k < end; k += 16) {
-    double p[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) p[i] = src[min(k + i, end - 1)];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc += k + i < end ? p[i] : 0.0;
-  }
-  run[v][q] = acc;
+  run[v][q] = run_fold<double>(a.partial + static_cast<int64_t>(v) * blocks, 1, q * per, min(blocks, (q + 1) * per));
   __syncthreads();
   if (threadIdx.x < 2) {
     double s = 0.0;
@@ -251,17 +242,12 @@ int launch_kl_divergence(const KlDivArgs& a, hipStream_t stream) {
   if (a.rows_out == nullptr && a.partial == nullptr) return -1;
   if (a.partial != nullptr && a.out == nullptr && (a.dst_sum == nullptr || a.dst_count == nullptr)) return -1;
   // element-aligned rows, and row r of both operands at one offset from a 16-B boundary
-  const int els = a.dt == DType::f32 ? 4 : 2;
+  const int els = dtype_bytes(a.dt);
   const uintptr_t xi = reinterpret_cast<uintptr_t>(a.input), ti = reinterpret_cast<uintptr_t>(a.target);
   if (xi % els != 0 || ti % els != 0 || (xi - ti) % 16 != 0) return -2;
   if (a.n > 1 && ((a.in_row_stride - a.tg_row_stride) * els) % 16 != 0) return -2;
   const int blocks = kl_divergence_blocks(a.n);
-  switch (a.dt) {
-    case DType::f32: launch_rows<0>(a, blocks, stream); break;
-    case DType::bf16: launch_rows<1>(a, blocks, stream); break;
-    case DType::f16: launch_rows<2>(a, blocks, stream); break;
-    default: return -1;
-  }
+  if (with_kind(a.dt, [&](auto kind) { return launch_rows<kind()>(a, blocks, stream), 0; }) != 0) return -1;
   if (a.partial != nullptr)
     hipLaunchKernelGGL(kl_divergence_finish_kernel, dim3(1), dim3(kFinishThreads), 0, stream, a, blocks);
   return static_cast<int>(hipGetLastError());

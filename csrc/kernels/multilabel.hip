@@ -295,13 +295,7 @@ int multilabel_max_topk_cols() { return 32 * kWave; }
 int launch_multilabel(const MultilabelArgs& a, hipStream_t stream) {
   if (a.n <= 0) return 0;
   const int grid = stream_grid(a.n, kWpb, 2048);
-  int rc;
-  switch (a.x_dt) {
-    case DType::f32: rc = launch_tk<0>(a, grid, stream); break;
-    case DType::bf16: rc = launch_tk<1>(a, grid, stream); break;
-    case DType::f16: rc = launch_tk<2>(a, grid, stream); break;
-    default: return -1;
-  }
+  const int rc = with_kind(a.x_dt, [&](auto kind) { return launch_tk<kind()>(a, grid, stream); });
   if (rc != 0) return rc;
   return static_cast<int>(hipGetLastError());
 }

@@ -43,15 +43,6 @@ __device__ __forceinline__ const void* score_row(const NdcgArgs& a, int64_t row)
   return static_cast<const char*>(a.x) + row * a.x_stride * kind_bytes<KIND>;
 }
 
-__device__ __forceinline__ int dt_size(DType dt) {
-  switch (dt) {
-    case DType::i64: case DType::f64: return 8;
-    case DType::f32: case DType::i32: return 4;
-    case DType::f16: case DType::bf16: case DType::i16: return 2;
-    default: return 1;
-  }
-}
-
 // gain of a relevance: t or 2^t - 1 (an integer t takes the exact power of two); +0.0 for
 // t == -0.0 and for the relevance of a bad row, so the bits of a gain order like its value
 __device__ __forceinline__ double gain_of(double t, int exponential) {
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void ndcg_narrow_kernel(NdcgArgs a) {
   const int lane = lane_id();
   const int wave = wave_id();
   const int C = a.c, K = a.k;
-  const int tsize = dt_size(a.t_dt);
+  const int tsize = dtype_bytes(a.t_dt);
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
   double acc = 0.0;  // this wave's rows, in row order (lane 0's copy is used)
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; row < a.n; row += nwaves) {
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void ndcg_wide_kernel(NdcgArgs a, int P) {
   unsigned long long* s_key = s_dyn;   // [P] (order key << 32) | column, sorted descending
   unsigned long long* s_gain = s_dyn + P;  // [P] gain bits: by column, then sorted descending
   const int C = a.c, K = a.k;
-  const int tsize = dt_size(a.t_dt);
+  const int tsize = dtype_bytes(a.t_dt);
   const int lane = lane_id();
   const int wave = wave_id();
   double acc = 0.0;  // thread 0: this block's rows, in row order
@@ -268,13 +259,7 @@ int launch_ndcg(const NdcgArgs& a, hipStream_t stream) {
     default: return -1;
   }
   const int blocks = ndcg_blocks(a.n, a.c);
-  int rc;
-  switch (a.x_dt) {
-    case DType::f32: rc = launch_kind<0>(a, blocks, stream); break;
-    case DType::bf16: rc = launch_kind<1>(a, blocks, stream); break;
-    case DType::f16: rc = launch_kind<2>(a, blocks, stream); break;
-    default: return -1;
-  }
+  const int rc = with_kind(a.x_dt, [&](auto kind) { return launch_kind<kind()>(a, blocks, stream); });
   if (rc || a.partial == nullptr) return rc;
   hipLaunchKernelGGL(ndcg_finish_kernel, dim3(1), dim3(kBlock), 0, stream, a.partial, blocks,
                      static_cast<double>(a.n), a.ndcg_sum, a.num_rows);

@@ -195,17 +195,13 @@ int launch_perplexity(const PerplexityArgs& a, hipStream_t stream) {
     const char* e = std::getenv("TORCHEVAL_AMD_PPL_U2");
     return e ? std::atoi(e) : -1;
   }();
-  const int els = a.in_dt == DType::f32 ? 4 : 2;
+  const int els = dtype_bytes(a.in_dt);
   // Unrolled body unless the batch already fills the CUs with many short rows (profiles/
   // k7_grid_cap_ab_r4.json: 2048 x 128256 bf16 125 -> 92 us, 65536 x 4096 fp32 177 vs 184 us).
   const bool u2 = u2_env >= 0 ? u2_env != 0 : (a.rows <= 16384 || a.v * els >= 65536);
   if (reinterpret_cast<uintptr_t>(a.input) % els != 0) return -2;  // split path needs element alignment
-  switch (a.in_dt) {
-    case DType::f32: launch_kind<0>(a, static_cast<int>(grid), vec, u2, stream); break;
-    case DType::bf16: launch_kind<1>(a, static_cast<int>(grid), vec, u2, stream); break;
-    case DType::f16: launch_kind<2>(a, static_cast<int>(grid), vec, u2, stream); break;
-    default: return -1;
-  }
+  const int g = static_cast<int>(grid);
+  if (with_kind(a.in_dt, [&](auto kind) { return launch_kind<kind()>(a, g, vec, u2, stream), 0; }) != 0) return -1;
   if (a.ordered_ws) return launch_ordered_sum(a.ordered_ws, 2, grid, a.out, stream);
   return static_cast<int>(hipGetLastError());
 }

@@ -121,12 +121,7 @@ int launch_kind(const RankArgs& a, hipStream_t s) {
 
 int launch_rank_scores(const RankArgs& a, hipStream_t stream) {
   if (a.n == 0) return 0;
-  switch (a.in_dt) {
-    case DType::f32: return launch_kind<0>(a, stream);
-    case DType::bf16: return launch_kind<1>(a, stream);
-    case DType::f16: return launch_kind<2>(a, stream);
-    default: return -1;
-  }
+  return with_kind(a.in_dt, [&](auto kind) { return launch_kind<kind()>(a, stream); });
 }
 
 }  // namespace tea

@@ -26,6 +26,7 @@
 // bit of ``err``, the only global atomic.  Integer sums: results are bit-identical run to run.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_partials.h"
 #include "tea_rowload.h"
 
 namespace tea {
@@ -250,19 +251,8 @@ __global__ __launch_bounds__(kFinishThreads) void segmentation_finish_kernel(Seg
     const int runs = kFinishThreads / np;
     const int per = (blocks + runs - 1) / runs;
     const int q = threadIdx.x / np, p = p0 + threadIdx.x % np;
-    if (q < runs) {
-      unsigned long long acc = 0;
-      const int end = min(blocks, (q + 1) * per);
-      const uint32_t* src = a.partial + p;
-      for (int k = q * per; k < end; k += 16) {
-        uint32_t v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = src[static_cast<int64_t>(min(k + i, end - 1)) * pairs];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc += k + i < end ? v[i] : 0u;
-      }
-      run[threadIdx.x] = acc;
-    }
+    if (q < runs)
+      run[threadIdx.x] = run_fold<unsigned long long>(a.partial + p, pairs, q * per, min(blocks, (q + 1) * per));
     __syncthreads();
     if (threadIdx.x < np) {
       unsigned long long acc = 0;
@@ -314,16 +304,11 @@ int launch_segmentation(const SegmentationArgs& a, hipStream_t stream) {
     if (!integer_dtype(a.in_dt)) return -1;
     hipLaunchKernelGGL((segmentation_count_kernel<kLabels, 1>), dim3(blocks), dim3(kB), lds, stream, a);
   } else {
-    const int els = a.in_dt == DType::f32 ? 4 : 2;
+    const int els = dtype_bytes(a.in_dt);
     if (reinterpret_cast<uintptr_t>(a.input) % els != 0) return -2;  // planes must be element-aligned
     if (a.arm == 0 && a.p > 1 && a.stride_p != 1) return -2;
     if (a.arm == 0 && els == 2 && a.c > 1 && a.stride_c % 8 != 0) return -2;  // one alignment for every class plane
-    switch (a.in_dt) {
-      case DType::f32: launch_scores<0>(a, blocks, lds, stream); break;
-      case DType::bf16: launch_scores<1>(a, blocks, lds, stream); break;
-      case DType::f16: launch_scores<2>(a, blocks, lds, stream); break;
-      default: return -1;
-    }
+    if (with_kind(a.in_dt, [&](auto kind) { return launch_scores<kind()>(a, blocks, lds, stream), 0; }) != 0) return -1;
   }
   hipLaunchKernelGGL(segmentation_finish_kernel, dim3(1), dim3(kFinishThreads), 0, stream, a, blocks);
   return static_cast<int>(hipGetLastError());

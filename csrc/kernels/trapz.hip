@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "tea_kernels.h"
+#include "tea_partials.h"
 
 namespace tea {
 namespace {
@@ -59,10 +60,7 @@ __global__ __launch_bounds__(kTT) void trapz_partial_kernel(const float* __restr
 __global__ __launch_bounds__(64) void trapz_combine_kernel(const double* __restrict__ part, int blocks,
                                                           float* __restrict__ out) {
   const int64_t row = blockIdx.x;
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < blocks; b += 64) acc += part[row * blocks + b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  const double acc = wave_strided_sum(part + row * blocks, blocks);
   if (threadIdx.x == 0) out[row] = static_cast<float>(0.5 * acc);
 }
 

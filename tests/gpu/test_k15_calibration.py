@@ -204,6 +204,19 @@ def test_more_rows_than_one_launch_covers(c, logits, native_calls):
         assert torch.equal(v1, v2)
 
 
+@pytest.mark.parametrize("n,c,n_bins", [(401, 33, 15), (401, 33, 256), (401, 33, 1), (257, 8, 15)])
+def test_finish_runs_full_short_and_empty(n, c, n_bins, native_calls):
+    """The finish launch's fold over runs of blocks (tea_partials.h run_fold), float32 probabilities.
+    401 rows of the wave arm are 101 blocks: with 15 bins 22 runs of 5 blocks (20 full, one of a
+    single block, one empty); with 256 bins one run of seven rounds of loads, the last holding 5;
+    with one bin 341 runs, 240 of them empty.  257 rows of the thread arm are two blocks.  (Two
+    blocks of the wave arm and the capped 1024 are reached by the tests above.)"""
+    assert n_bins <= K.max_bins()
+    x, t = scores(n, c, 600 + n_bins, False, torch.float32)
+    check(x.to(DEV), t.to(DEV), x, t, n_bins, False)
+    assert len(native_calls) == 4
+
+
 # ----------------------------------------------------------------------------- bins
 @pytest.mark.parametrize("c", [3, 40])
 @pytest.mark.parametrize("n_bins", [10, 15, 100])

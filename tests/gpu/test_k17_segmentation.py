@@ -310,6 +310,30 @@ def test_label_maps_of_every_integer_dtype(native_calls):
     assert len(native_calls) == 14
 
 
+@pytest.mark.parametrize("n,p", [(3, K.SPAN + 1), (101, 5)])
+@pytest.mark.parametrize("c", [1, 341, 342, 1024])
+def test_finish_chunks_and_runs_of_label_maps(c, n, p, native_calls):
+    """The finish launch's fold over runs of blocks (tea_partials.h run_fold) on label maps, the
+    counts exact against ``bincount``.  The 3 c pairs are taken 1024 at a time: one class is 3 pairs
+    and 341 runs, 341 classes one chunk of one run, 342 a second chunk of 2 pairs with 512 runs, 1024
+    three full chunks; each over 6 blocks (most runs empty) and over 101.  A second update
+    accumulates into the same states."""
+    assert c <= K.max_classes() and n * -(-p // K.SPAN) == (6 if n == 3 else 101)  # one block per span
+    g = torch.Generator().manual_seed(7000 + c + n)
+    pred = torch.randint(0, c, (n, p), generator=g)
+    t = torch.where(torch.rand(n, p, generator=g) < 0.5, pred, torch.randint(0, c, (n, p), generator=g))
+    want = [torch.bincount(v.reshape(-1), minlength=c).double() for v in (pred[pred == t], pred, t)]
+    pd, td = pred.to(DEV), t.to(DEV)
+    assert K.arm(pd) == "label"
+    m = MeanIoU(num_classes=c, device=DEV).update(pd, td)
+    for name, w in zip(STATES, want):
+        assert torch.equal(getattr(m, name).cpu(), w), name
+    m.update(pd, td)
+    for name, w in zip(STATES, want):
+        assert torch.equal(getattr(m, name).cpu(), 2 * w), name
+    assert len(native_calls) == 2
+
+
 # ----------------------------------------------------------------------------- label structure
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_one_label_images_and_sixty_four_labels_in_a_wave(dtype, native_calls):

@@ -180,6 +180,25 @@ def test_more_rows_than_the_grid_covers_and_two_runs(logits, native_calls):
     assert torch.equal(a.kl_sum, b.kl_sum) and torch.equal(a.num_rows, b.num_rows) and float(a.num_rows) == 2 * n
 
 
+@pytest.mark.parametrize("logits", [True, False])
+@pytest.mark.parametrize("n", [257, 4096])
+def test_finish_runs_full_short_and_empty(n, logits, native_calls):
+    """The finish launch's fold over runs of blocks (tea_partials.h run_fold) at three columns.
+    257 rows are 65 blocks: 32 runs of two, one of a single block, 31 empty.  4096 rows are the
+    capped 1024 blocks with no row left over: 64 runs of exactly one round of 16 loads.  (One block
+    and the capped grid with grid-stride rows are reached by the tests above.)  At 257 rows also
+    with every third row masked off, so that the count is not the number of rows."""
+    x, t = pair(n, 3, 3000 + n, logits, torch.float32)
+    want = oracle_rows(n, 3, 3000 + n, logits, torch.float32)
+    xd, td = x.to(DEV), t.to(DEV)
+    check(xd, td, want, logits, f"{n}x3")
+    assert len(native_calls) == 4
+    if n == 257:
+        mask = torch.arange(n) % 3 != 0
+        check(xd, td, np.where(mask.numpy(), want, 0.0), logits, f"{n}x3 masked", mask.to(DEV))
+        assert len(native_calls) == 8
+
+
 def test_nearly_equal_distributions_keep_sign_and_size(native_calls):
     """KL about 1e-6: the bound's floor is absolute, so this checks sign and size only (no value is
     negative beyond the floor and none exceeds 1e-5)."""

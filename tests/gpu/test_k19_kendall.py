@@ -109,6 +109,10 @@ def test_35_tiles_with_odd_run_counts(levels):
     check(*pair(70001, levels, 4))
 
 
+def test_66_tiles_the_finish_wave_takes_a_second_round():
+    check(*pair(65 * T + 5, 50, 5))
+
+
 def test_tie_runs_straddle_one_tile_boundary():
     n = 2 * T + 4
     g = torch.Generator().manual_seed(1)
