@@ -301,6 +301,15 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.kl_divergence(x, t)
         return make
 
+    def inception(cls):
+        def make():
+            x = torch.randn(B, C, device=dev) * 3
+            if cls:
+                m = M.InceptionScore(model=torch.nn.Identity(), num_classes=C, device=dev)
+                return lambda: m.update_logits(x).compute()
+            return lambda: F.inception_score(x)
+        return make
+
     def rp_queries():
         Q = 1000 if s >= 1 else 10
         x, y, q = rand(N1M), randint(2, N1M), randint(Q, N1M)
@@ -468,6 +477,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "kernel_inception_distance 10000x2048, 100 subsets of 1000 (K20)": kid(False, 10000, 2048),
         "KernelInceptionDistance.compute 10000x2048, 100 subsets of 1000 (K20)": kid(True, 10000, 2048),
         "kernel_inception_distance 10000x64, 100 subsets of 1000 (K20)": kid(False, 10000, 64),
+        "inception_score 8192x1000, 10 splits (K21)": inception(False),
+        "InceptionScore.update_logits+compute 8192x1000, 10 splits (K21)": inception(True),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),
         "WeightedCalibration(64 tasks).update 8192x1000 (K5b)": k5b(M.WeightedCalibration, "wc"),
         "WindowedClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.WindowedClickThroughRate, "ctr"),

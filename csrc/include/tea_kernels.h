@@ -893,3 +893,42 @@ int64_t kid_items(int64_t m);  // tiles per subset: T (T + 1) / 2 of XX, as many
 int launch_kid_gram(const KidGramArgs& a, hipStream_t stream);
 int launch_kid_finish(const KidFinishArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K21: Inception Score (csrc/kernels/inception_score.hip; docs/parity.md, "Not in the reference").
+// Row i of the [n, c] logits belongs to split (first + i) mod s.  inception_rows_kernel reads every
+// row once and writes, per block, the FP64 column sums of the softmax probabilities of its rows,
+// the sum of their negative entropies and their number; inception_finish_kernel adds the blocks'
+// partials in block order into the three states; inception_value_kernel forms the splits' log
+// scores and the mean and population standard deviation of their exponentials.
+constexpr int kInceptionMaxColumns = 2048;  // a wave holds one row in registers, 32 values per lane
+constexpr int kInceptionMaxSplits = 64;     // one lane per split in the value launch's last step
+constexpr int kInceptionMaxBlocks = 1024;   // grid cap of the row launch: splits x blocks per split
+constexpr int kInceptionWavesPerBlock = 4;
+constexpr int kInceptionNarrowColumns = 256;  // rows this narrow or narrower ...
+constexpr int kInceptionRowsPerWaveNarrow = 32;  // ... aim at this many rows per wave,
+constexpr int kInceptionRowsPerWaveWide = 8;     // wider ones at this many
+struct InceptionArgs {
+  const void* logits = nullptr;  // [n, c], unit stride along c, rows element-aligned
+  DType dt = DType::f32;         // f32 / bf16 / f16
+  int64_t row_stride = 0;        // elements, >= 0
+  int64_t n = 0;                 // 1 .. 2^31 - 1
+  int c = 0;                     // 1 .. kInceptionMaxColumns
+  int splits = 0;                // 1 .. kInceptionMaxSplits
+  int first = 0;                 // 0 .. splits - 1: the split of row 0
+  double* partial = nullptr;     // [splits * inception_blocks(n, splits, c), c + 2] scratch
+  double* prob_sum = nullptr;    // [splits, c] +=
+  double* neg_entropy_sum = nullptr;  // [splits] +=
+  double* num_rows = nullptr;    // [splits] +=
+};
+// Blocks per split of the row launch.  A split has about n / splits rows, a block four waves; a wave
+// should walk kInceptionRowsPerWave{Narrow, Wide} rows, so that the block's one [c + 2] partial
+// (8 bytes per column, written here and read by the finish launch) stays small against the rows it
+// stands for, until splits x blocks reaches kInceptionMaxBlocks; past that the waves take more rows.
+int inception_blocks(int64_t n, int splits, int c);
+int launch_inception_update(const InceptionArgs& a, hipStream_t stream);
+// split_log[s] (NaN for a split without rows) and out[0 .. 2) = mean and population standard
+// deviation of exp(split_log) over the splits with rows; 1 <= splits <= kInceptionMaxSplits, c >= 1
+int launch_inception_value(const double* prob_sum, const double* neg_entropy_sum, const double* num_rows,
+                           int splits, int64_t c, double* split_log, float* out, hipStream_t stream);
+}  // namespace tea

@@ -128,6 +128,7 @@ enum class Scratch : int {
   kCorrcoefPartials = 18,   // K16
   kSegmentationPartials = 19,  // K17
   kKlDivPartials = 20,      // K18
+  kInceptionPartials = 21,  // K21
 };
 
 // `capacity`, when given, receives the buffer's size in bytes (>= bytes)

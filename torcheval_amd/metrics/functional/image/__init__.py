@@ -1,5 +1,6 @@
 """Image metrics, functional API (parity: functional/image/psnr.py)."""
 
+from torcheval_amd.metrics.functional.image.inception_score import inception_score
 from torcheval_amd.metrics.functional.image.kid import kernel_inception_distance
 from torcheval_amd.metrics.functional.image.psnr import (
     peak_signal_noise_ratio,
@@ -16,3 +17,4 @@ __all__ = [
     "structural_similarity",
 ]
 __doc_name__ = "Image Metrics"
+__doc_extras__ = ["inception_score"]  # documented, not a reference name

@@ -235,3 +235,19 @@ class FIDInceptionV3(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=False)
         return self.model(x)
+
+
+class InceptionV3Logits(FIDInceptionV3):
+    """Inception Score classifier: the same bilinear resize to 299x299 as ``FIDInceptionV3``, then
+    Inception-v3 with its 1000-way ``fc`` kept: ``[B, 1000]`` class logits.  A subclass, so that the
+    image checks of the FID family (float32 images in [0, 1] for the default model) apply."""
+
+    def __init__(self, weights: Optional[str] = "DEFAULT", weights_path: Optional[str] = None) -> None:
+        nn.Module.__init__(self)
+        self.model = inception_v3(weights_path=weights_path)
+        if weights_path is None and weights is not None:
+            warnings.warn(
+                "Pretrained Inception-v3 weights are not available offline; InceptionV3Logits is "
+                "randomly initialised (pass weights_path=... to load a local checkpoint).",
+                RuntimeWarning,
+            )
