@@ -244,6 +244,18 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.kernel_inception_distance(real, fake, subset_size=m)
         return make
 
+    def prdc(cls, dc, rows, d):
+        def make():
+            rows_ = rows if s >= 1 else n(rows // 40)
+            real, fake = rand(rows_, d), rand(rows_, d) + 0.02
+            if cls:
+                metric = (M.DensityCoverage if dc else M.ImprovedPrecisionRecall)(
+                    model=torch.nn.Identity(), feature_dim=d, device=dev)
+                metric.update_activations(real, True).update_activations(fake, False)
+                return lambda: metric.compute()
+            return lambda: (F.density_coverage if dc else F.improved_precision_recall)(real, fake)
+        return make
+
     def ndcg(cls):
         def make():
             x, t = rand(B, C), randint(5, B, C)
@@ -477,6 +489,9 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "kernel_inception_distance 10000x2048, 100 subsets of 1000 (K20)": kid(False, 10000, 2048),
         "KernelInceptionDistance.compute 10000x2048, 100 subsets of 1000 (K20)": kid(True, 10000, 2048),
         "kernel_inception_distance 10000x64, 100 subsets of 1000 (K20)": kid(False, 10000, 64),
+        "improved_precision_recall 10000x2048, k=3 (K22)": prdc(False, False, 10000, 2048),
+        "DensityCoverage.compute 10000x2048, k=5 (K22)": prdc(True, True, 10000, 2048),
+        "density_coverage 10000x64, k=5 (K22)": prdc(False, True, 10000, 64),
         "inception_score 8192x1000, 10 splits (K21)": inception(False),
         "InceptionScore.update_logits+compute 8192x1000, 10 splits (K21)": inception(True),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),

@@ -932,3 +932,86 @@ int launch_inception_update(const InceptionArgs& a, hipStream_t stream);
 int launch_inception_value(const double* prob_sum, const double* neg_entropy_sum, const double* num_rows,
                            int splits, int64_t c, double* split_log, float* out, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K22: improved precision / recall and density / coverage (csrc/kernels/prdc.hip; docs/parity.md,
+// "Not in the reference").  All four are k-nearest-neighbour statistics of the squared distances
+// d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 <a, b>) between two feature sets.  prdc_tile_kernel walks
+// 128 x 128 FP32-MFMA tiles of <a, b> (K20's main loop) and keeps, per query row, either the k
+// smallest d2 (Knn) or the count of d2 <= rad2[col] and the smallest d2 (Cross) over the column
+// tiles of its block; no distance is ever written to memory.
+constexpr int kPrdcTile = 128;         // rows and columns of one tile
+constexpr int kPrdcMaxK = 8;           // neighbours kept per row
+constexpr int kPrdcCUs = 256;          // compute units of the MI355X, which the group rule balances over
+constexpr int kPrdcMaxGroups = 16;     // the rule's largest G: at most 32 lists per row
+constexpr int kPrdcBlockStages = 12;   // a block's fixed cost in the rule, in 32-wide k-steps of one tile
+constexpr int kPrdcHitsRows = 256;     // rows per block of prdc_hits_kernel
+// Column groups G of a pass of n_query rows of width d over n_ref columns: block (p, g) owns the
+// 128-row panel p and walks the column tiles g, g + G, ...  `groups` >= 1 is taken as given (clamped
+// to the number of column tiles).  0 is the rule: the G in 1 .. min(column tiles, kPrdcMaxGroups)
+// with the smallest modelled time of the busiest CU (the smallest such G on a tie),
+//   c (t ceil(d / 32) + kPrdcBlockStages) (c == 1 ? 4 : 3),   c = ceil(panels G / kPrdcCUs),  t = ceil(tiles / G):
+// a CU is handed c blocks of t tiles each, a block costs about 12 k-steps before its first tile, and
+// a block alone on its CU walks a tile in 2/3 of the time two resident blocks share, not in 1/2.
+// The model follows the measured times of profiles/prdc_r18.json to a few percent.  Every block
+// writes two lists per row (one per 64-column half of its tiles): 2 G lists in all.
+int64_t prdc_groups(int64_t n_query, int64_t n_ref, int64_t d, int64_t groups);
+struct PrdcNormsArgs {
+  const float* real = nullptr;  // [n_r, D], unit stride along D
+  const float* fake = nullptr;  // [n_f, D]
+  int64_t real_stride = 0;      // row strides in elements
+  int64_t fake_stride = 0;
+  int64_t n_r = 0;
+  int64_t n_f = 0;
+  int64_t d = 0;
+  double* norms_real = nullptr;  // [n_r]: FP64 sums of squares
+  double* norms_fake = nullptr;  // [n_f]
+};
+struct PrdcTileArgs {
+  const float* query = nullptr;  // [n_q, D], unit stride along D
+  const float* ref = nullptr;    // [n_ref, D] (Knn: the query set itself)
+  int64_t query_stride = 0;
+  int64_t ref_stride = 0;
+  int64_t n_q = 0;
+  int64_t n_ref = 0;
+  int64_t d = 0;
+  const double* norms_q = nullptr;    // [n_q]
+  const double* norms_ref = nullptr;  // [n_ref]
+  int groups = 0;                     // G >= 1 (prdc_groups)
+  // Knn
+  int k = 0;                   // 1 .. kPrdcMaxK
+  double* partial = nullptr;   // [n_q, 2 G, k]: ascending, +inf in the slots never filled
+  // Cross
+  const double* radii_ref = nullptr;  // [n_ref]: squared radii of the reference rows
+  uint32_t* counts = nullptr;         // [n_q, 2 G]
+  double* mins = nullptr;             // [n_q, 2 G]: +inf where the list saw no column
+};
+struct PrdcFinishArgs {
+  // cross partials of the pass fake -> real ([n_f, lists_f]) and real -> fake ([n_r, lists_r])
+  const uint32_t* counts_fake = nullptr;
+  const double* mins_fake = nullptr;
+  const uint32_t* counts_real = nullptr;
+  const double* mins_real = nullptr;
+  const double* radii_real = nullptr;  // [n_r]
+  int64_t n_r = 0;
+  int64_t n_f = 0;
+  int lists_r = 0;
+  int lists_f = 0;
+  int k = 0;
+  int64_t* block_tallies = nullptr; // [prdc_hits_blocks(n_r, n_f), 4] scratch
+  int32_t* hits_real = nullptr;     // [n_r]
+  int32_t* hits_fake = nullptr;     // [n_f]
+  double* nearest_real = nullptr;   // [n_r]
+  double* nearest_fake = nullptr;   // [n_f]
+  int64_t* tallies = nullptr;       // [4]: precise rows, recalled rows, total hits_fake, covered rows
+  float* values = nullptr;          // [4]: precision, recall, density, coverage
+};
+int launch_prdc_norms(const PrdcNormsArgs& a, hipStream_t stream);
+int launch_prdc_knn(const PrdcTileArgs& a, hipStream_t stream);
+int launch_prdc_cross(const PrdcTileArgs& a, hipStream_t stream);
+// radii[row] <- the k-th smallest of the row's `lists` ascending k-lists
+int launch_prdc_radii(const double* partial, int64_t n, int lists, int k, double* radii, hipStream_t stream);
+// blocks of prdc_hits_kernel: kPrdcHitsRows rows of the generated side each, then of the real side
+int64_t prdc_hits_blocks(int64_t n_r, int64_t n_f);
+int launch_prdc_finish(const PrdcFinishArgs& a, hipStream_t stream);  // two launches
+}  // namespace tea

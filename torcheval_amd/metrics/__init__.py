@@ -12,6 +12,7 @@ from torcheval_amd.metrics.image import PeakSignalNoiseRatio
 from torcheval_amd.metrics.image import StructuralSimilarity  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.image import KernelInceptionDistance  # likewise
 from torcheval_amd.metrics.image import InceptionScore  # likewise
+from torcheval_amd.metrics.image import DensityCoverage, ImprovedPrecisionRecall  # likewise
 from torcheval_amd.metrics.metric import Metric
 from torcheval_amd.metrics.ranking import (
     ClickThroughRate,

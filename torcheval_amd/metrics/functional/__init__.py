@@ -9,6 +9,7 @@ from torcheval_amd.metrics.functional.image import peak_signal_noise_ratio
 from torcheval_amd.metrics.functional.image import structural_similarity  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.functional.image import kernel_inception_distance  # likewise
 from torcheval_amd.metrics.functional.image import inception_score  # likewise
+from torcheval_amd.metrics.functional.image import density_coverage, improved_precision_recall  # likewise
 from torcheval_amd.metrics.functional.ranking import (
     click_through_rate,
     frequency_at_k,

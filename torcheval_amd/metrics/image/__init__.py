@@ -6,10 +6,18 @@ resolves on first access), so importing the metrics package never needs a vision
 
 from torcheval_amd.metrics.image.inception_score import InceptionScore
 from torcheval_amd.metrics.image.kid import KernelInceptionDistance
+from torcheval_amd.metrics.image.prdc import DensityCoverage, ImprovedPrecisionRecall
 from torcheval_amd.metrics.image.psnr import PeakSignalNoiseRatio
 from torcheval_amd.metrics.image.ssim import StructuralSimilarity
 
-__all__ = ["FrechetInceptionDistance", "KernelInceptionDistance", "PeakSignalNoiseRatio", "StructuralSimilarity"]
+__all__ = [
+    "DensityCoverage",
+    "FrechetInceptionDistance",
+    "ImprovedPrecisionRecall",
+    "KernelInceptionDistance",
+    "PeakSignalNoiseRatio",
+    "StructuralSimilarity",
+]
 __doc_name__ = "Image Metrics"
 __doc_extras__ = ["InceptionScore"]  # documented, not a reference name
 
