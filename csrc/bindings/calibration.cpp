@@ -14,12 +14,6 @@ namespace {
 
 using namespace tea_torch;
 
-double* bins_state(const Tensor& t, const Tensor& ref, int64_t n_bins, const char* what, const char* name) {
-  TORCH_CHECK(t.scalar_type() == at::kDouble && t.is_contiguous() && t.numel() == n_bins && t.device() == ref.device(),
-              what, ": ", name, " must be a contiguous float64 [n_bins] tensor on the inputs' device");
-  return t.data_ptr<double>();
-}
-
 // the checks and the argument block both ops share; `tg` keeps a contiguous copy of the target alive
 tea::CalibrationArgs calibration_args(const Tensor& input, const Tensor& target, int64_t n_bins, bool from_logits,
                                       const optional<Tensor>& err, Tensor& tg, const char* what) {
@@ -64,9 +58,9 @@ void calibration_update(const Tensor& input, const Tensor& target, int64_t n_bin
                         const optional<Tensor>& err) {
   Tensor tg;
   tea::CalibrationArgs a = calibration_args(input, target, n_bins, from_logits, err, tg, "calibration_update");
-  a.dst[0] = bins_state(bin_count, input, n_bins, "calibration_update", "bin_count");
-  a.dst[1] = bins_state(correct_sum, input, n_bins, "calibration_update", "correct_sum");
-  a.dst[2] = bins_state(conf_sum, input, n_bins, "calibration_update", "conf_sum");
+  a.dst[0] = f64_buf(bin_count, input, n_bins, "calibration_update", "bin_count");
+  a.dst[1] = f64_buf(correct_sum, input, n_bins, "calibration_update", "correct_sum");
+  a.dst[2] = f64_buf(conf_sum, input, n_bins, "calibration_update", "conf_sum");
   a.accumulate = 1;
   if (a.n == 0) return;
   DeviceGuard guard(input.device());
@@ -99,9 +93,9 @@ void calibration_value(const Tensor& bin_count, const Tensor& correct_sum, const
   const int64_t n_bins = bin_count.numel();
   TORCH_CHECK(n_bins >= 1 && n_bins < (int64_t{1} << 31), "calibration_value: 1 .. 2^31 - 1 bins");
   TORCH_CHECK(norm >= 0 && norm <= 2, "calibration_value: norm must be 0 (l1), 1 (max) or 2 (l2)");
-  const double* n = bins_state(bin_count, bin_count, n_bins, "calibration_value", "bin_count");
-  const double* k = bins_state(correct_sum, bin_count, n_bins, "calibration_value", "correct_sum");
-  const double* f = bins_state(conf_sum, bin_count, n_bins, "calibration_value", "conf_sum");
+  const double* n = f64_buf(bin_count, bin_count, n_bins, "calibration_value", "bin_count");
+  const double* k = f64_buf(correct_sum, bin_count, n_bins, "calibration_value", "correct_sum");
+  const double* f = f64_buf(conf_sum, bin_count, n_bins, "calibration_value", "conf_sum");
   float* o = f32_out(out, bin_count, 1, "out");
   DeviceGuard guard(bin_count.device());
   check_launch(tea::launch_calibration_value(n, k, f, static_cast<int>(n_bins), static_cast<int>(norm), o,

@@ -13,28 +13,13 @@ namespace {
 
 using namespace tea_torch;
 
-// float32 [n >= 1, D] features with unit stride along D
-void check_features(const Tensor& t, const char* name) {
-  check_gpu(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1 &&
-                  (t.stride(1) == 1 || t.size(1) == 1) && t.stride(0) >= 0,
-              "kid_gram: ", name, " must be a float32 [n, D] tensor with unit stride along D");
-}
-
-// a contiguous float64 tensor of `numel` elements on `ref`'s device
-double* f64_buf(const Tensor& t, const Tensor& ref, int64_t numel, const char* what, const char* name) {
-  TORCH_CHECK(t.scalar_type() == at::kDouble && t.is_contiguous() && t.numel() == numel && t.device() == ref.device(),
-              what, ": ", name, " must be a contiguous float64 tensor of ", numel, " elements on the inputs' device");
-  return t.data_ptr<double>();
-}
-
 // partials[S, kid_items(m)] (float64) <- per tile of the three Gram blocks of every subset, the sum
 // of (gamma <a, b> + coef)^degree over the pairs it counts.  idx_r / idx_f are [S, m] int32 rows of
 // `real` / `fake`; indices in [0, n) are the caller's precondition (the kernel clamps).  One launch
 void kid_gram(const Tensor& real, const Tensor& fake, const Tensor& idx_r, const Tensor& idx_f, double gamma,
               double coef, int64_t degree, const Tensor& partials) {
-  check_features(real, "real");
-  check_features(fake, "fake");
+  check_features(real, "kid_gram", "real");
+  check_features(fake, "kid_gram", "fake");
   TORCH_CHECK(fake.device() == real.device() && fake.size(1) == real.size(1),
               "kid_gram: real and fake must share their device and feature width");
   TORCH_CHECK(idx_r.scalar_type() == at::kInt && idx_r.is_contiguous() && idx_r.dim() == 2 && idx_r.size(0) >= 1 &&

@@ -14,32 +14,17 @@ namespace {
 
 using namespace tea_torch;
 
-// float32 [n >= 1, D >= 1] features with unit stride along D
-void check_features(const Tensor& t, const char* what, const char* name) {
-  check_gpu(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1 &&
-                  (t.stride(1) == 1 || t.size(1) == 1) && t.stride(0) >= 0,
-              what, ": ", name, " must be a float32 [n, D] tensor with unit stride along D");
+// check_features of tea_torch.h, and sizes that the tile kernels index in 32 bits
+void check_tile_features(const Tensor& t, const char* what, const char* name) {
+  check_features(t, what, name);
   TORCH_CHECK(t.size(0) < (int64_t{1} << 31) - tea::kPrdcTile && t.size(1) < (int64_t{1} << 31) - 64, what, ": ",
               name, " must have fewer than 2^31 - 128 rows and 2^31 - 64 columns");
 }
 
-// a contiguous tensor of `dtype` with `numel` elements on `ref`'s device
-void* buf(const Tensor& t, at::ScalarType dtype, const Tensor& ref, int64_t numel, const char* what,
-          const char* name) {
-  TORCH_CHECK(t.scalar_type() == dtype && t.is_contiguous() && t.numel() == numel && t.device() == ref.device(),
-              what, ": ", name, " must be a contiguous ", dtype, " tensor of ", numel,
-              " elements on the inputs' device");
-  return t.data_ptr();
-}
-double* f64(const Tensor& t, const Tensor& ref, int64_t numel, const char* what, const char* name) {
-  return static_cast<double*>(buf(t, at::kDouble, ref, numel, what, name));
-}
-
 tea::PrdcTileArgs tile_args(const Tensor& query, const Tensor& ref, const Tensor& norms_q, const Tensor& norms_ref,
                             int64_t groups, const char* what) {
-  check_features(query, what, "query");
-  check_features(ref, what, "ref");
+  check_tile_features(query, what, "query");
+  check_tile_features(ref, what, "ref");
   TORCH_CHECK(ref.device() == query.device() && ref.size(1) == query.size(1), what,
               ": both feature sets must share their device and width");
   TORCH_CHECK(groups >= 0, what, ": groups must be >= 0 (0: the rule of prdc_groups), got ", groups);
@@ -51,16 +36,16 @@ tea::PrdcTileArgs tile_args(const Tensor& query, const Tensor& ref, const Tensor
   a.n_q = query.size(0);
   a.n_ref = ref.size(0);
   a.d = query.size(1);
-  a.norms_q = f64(norms_q, query, a.n_q, what, "the query norms");
-  a.norms_ref = f64(norms_ref, query, a.n_ref, what, "the reference norms");
+  a.norms_q = f64_buf(norms_q, query, a.n_q, what, "the query norms");
+  a.norms_ref = f64_buf(norms_ref, query, a.n_ref, what, "the reference norms");
   a.groups = static_cast<int>(tea::prdc_groups(a.n_q, a.n_ref, a.d, groups));
   return a;
 }
 
 // norms_real[n_r], norms_fake[n_f] (float64) <- the FP64 sums of squares of the rows.  One launch
 void prdc_norms(const Tensor& real, const Tensor& fake, const Tensor& norms_real, const Tensor& norms_fake) {
-  check_features(real, "prdc_norms", "real");
-  check_features(fake, "prdc_norms", "fake");
+  check_tile_features(real, "prdc_norms", "real");
+  check_tile_features(fake, "prdc_norms", "fake");
   TORCH_CHECK(fake.device() == real.device() && fake.size(1) == real.size(1),
               "prdc_norms: real and fake must share their device and feature width");
   DeviceGuard guard(real.device());
@@ -72,8 +57,8 @@ void prdc_norms(const Tensor& real, const Tensor& fake, const Tensor& norms_real
   a.n_r = real.size(0);
   a.n_f = fake.size(0);
   a.d = real.size(1);
-  a.norms_real = f64(norms_real, real, a.n_r, "prdc_norms", "norms_real");
-  a.norms_fake = f64(norms_fake, real, a.n_f, "prdc_norms", "norms_fake");
+  a.norms_real = f64_buf(norms_real, real, a.n_r, "prdc_norms", "norms_real");
+  a.norms_fake = f64_buf(norms_fake, real, a.n_f, "prdc_norms", "norms_fake");
   check_launch(tea::launch_prdc_norms(a, stream_for(real)), "prdc_norms");
 }
 
@@ -86,7 +71,7 @@ void prdc_knn(const Tensor& feats, const Tensor& norms, int64_t k, int64_t group
               "prdc_knn: partial must be [n, 2 G, k] with G = ", a.groups);
   DeviceGuard guard(feats.device());
   a.k = static_cast<int>(k);
-  a.partial = f64(partial, feats, a.n_q * 2 * a.groups * k, "prdc_knn", "partial");
+  a.partial = f64_buf(partial, feats, a.n_q * 2 * a.groups * k, "prdc_knn", "partial");
   check_launch(tea::launch_prdc_knn(a, stream_for(feats)), "prdc_knn");
 }
 
@@ -98,7 +83,7 @@ void prdc_radii(const Tensor& partial, const Tensor& radii) {
                   partial.size(1) < (int64_t{1} << 24) && partial.size(2) >= 1 && partial.size(2) <= tea::kPrdcMaxK,
               "prdc_radii: partial must be a contiguous float64 [n, lists, k <= ", tea::kPrdcMaxK, "] tensor");
   DeviceGuard guard(partial.device());
-  double* out = f64(radii, partial, partial.size(0), "prdc_radii", "radii");
+  double* out = f64_buf(radii, partial, partial.size(0), "prdc_radii", "radii");
   check_launch(tea::launch_prdc_radii(partial.data_ptr<double>(), partial.size(0), static_cast<int>(partial.size(1)),
                                       static_cast<int>(partial.size(2)), out, stream_for(partial)),
                "prdc_radii");
@@ -110,12 +95,12 @@ void prdc_cross(const Tensor& query, const Tensor& ref, const Tensor& norms_q, c
                 const Tensor& radii_ref, int64_t groups, const Tensor& counts, const Tensor& mins) {
   tea::PrdcTileArgs a = tile_args(query, ref, norms_q, norms_ref, groups, "prdc_cross");
   DeviceGuard guard(query.device());
-  a.radii_ref = f64(radii_ref, query, a.n_ref, "prdc_cross", "radii_ref");
+  a.radii_ref = f64_buf(radii_ref, query, a.n_ref, "prdc_cross", "radii_ref");
   TORCH_CHECK(counts.dim() == 2 && counts.size(0) == a.n_q && counts.size(1) == 2 * a.groups &&
                   mins.sizes() == counts.sizes(),
               "prdc_cross: counts and mins must be [n_q, 2 G] with G = ", a.groups);
-  a.counts = static_cast<uint32_t*>(buf(counts, at::kInt, query, a.n_q * 2 * a.groups, "prdc_cross", "counts"));
-  a.mins = f64(mins, query, a.n_q * 2 * a.groups, "prdc_cross", "mins");
+  a.counts = static_cast<uint32_t*>(dense_buf(counts, at::kInt, query, a.n_q * 2 * a.groups, "prdc_cross", "counts"));
+  a.mins = f64_buf(mins, query, a.n_q * 2 * a.groups, "prdc_cross", "mins");
   check_launch(tea::launch_prdc_cross(a, stream_for(query)), "prdc_cross");
 }
 
@@ -141,19 +126,20 @@ void prdc_finish(const Tensor& counts_fake, const Tensor& mins_fake, const Tenso
   a.lists_r = static_cast<int>(counts_real.size(1));
   a.k = static_cast<int>(k);
   a.counts_fake =
-      static_cast<uint32_t*>(buf(counts_fake, at::kInt, ref, a.n_f * a.lists_f, "prdc_finish", "counts_fake"));
-  a.mins_fake = f64(mins_fake, ref, a.n_f * a.lists_f, "prdc_finish", "mins_fake");
+      static_cast<uint32_t*>(dense_buf(counts_fake, at::kInt, ref, a.n_f * a.lists_f, "prdc_finish", "counts_fake"));
+  a.mins_fake = f64_buf(mins_fake, ref, a.n_f * a.lists_f, "prdc_finish", "mins_fake");
   a.counts_real =
-      static_cast<uint32_t*>(buf(counts_real, at::kInt, ref, a.n_r * a.lists_r, "prdc_finish", "counts_real"));
-  a.mins_real = f64(mins_real, ref, a.n_r * a.lists_r, "prdc_finish", "mins_real");
-  a.radii_real = f64(radii_real, ref, a.n_r, "prdc_finish", "radii_real");
-  a.block_tallies = static_cast<int64_t*>(
-      buf(block_tallies, at::kLong, ref, 4 * tea::prdc_hits_blocks(a.n_r, a.n_f), "prdc_finish", "block_tallies"));
-  a.hits_real = static_cast<int32_t*>(buf(hits_real, at::kInt, ref, a.n_r, "prdc_finish", "hits_real"));
-  a.hits_fake = static_cast<int32_t*>(buf(hits_fake, at::kInt, ref, a.n_f, "prdc_finish", "hits_fake"));
-  a.nearest_real = f64(nearest_real, ref, a.n_r, "prdc_finish", "nearest_real");
-  a.nearest_fake = f64(nearest_fake, ref, a.n_f, "prdc_finish", "nearest_fake");
-  a.tallies = static_cast<int64_t*>(buf(tallies, at::kLong, ref, 4, "prdc_finish", "tallies"));
+      static_cast<uint32_t*>(dense_buf(counts_real, at::kInt, ref, a.n_r * a.lists_r, "prdc_finish", "counts_real"));
+  a.mins_real = f64_buf(mins_real, ref, a.n_r * a.lists_r, "prdc_finish", "mins_real");
+  a.radii_real = f64_buf(radii_real, ref, a.n_r, "prdc_finish", "radii_real");
+  a.block_tallies = static_cast<int64_t*>(dense_buf(block_tallies, at::kLong, ref,
+                                                    4 * tea::prdc_hits_blocks(a.n_r, a.n_f), "prdc_finish",
+                                                    "block_tallies"));
+  a.hits_real = static_cast<int32_t*>(dense_buf(hits_real, at::kInt, ref, a.n_r, "prdc_finish", "hits_real"));
+  a.hits_fake = static_cast<int32_t*>(dense_buf(hits_fake, at::kInt, ref, a.n_f, "prdc_finish", "hits_fake"));
+  a.nearest_real = f64_buf(nearest_real, ref, a.n_r, "prdc_finish", "nearest_real");
+  a.nearest_fake = f64_buf(nearest_fake, ref, a.n_f, "prdc_finish", "nearest_fake");
+  a.tallies = static_cast<int64_t*>(dense_buf(tallies, at::kLong, ref, 4, "prdc_finish", "tallies"));
   a.values = f32_out(values, ref, 4, "values");
   check_launch(tea::launch_prdc_finish(a, stream_for(ref)), "prdc_finish");
 }

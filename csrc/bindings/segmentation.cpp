@@ -14,12 +14,6 @@ namespace {
 
 using namespace tea_torch;
 
-double* class_state(const Tensor& t, const Tensor& ref, int64_t c, const char* what, const char* name) {
-  TORCH_CHECK(t.scalar_type() == at::kDouble && t.is_contiguous() && t.numel() == c && t.device() == ref.device(),
-              what, ": ", name, " must be a contiguous float64 [num_classes] tensor on the inputs' device");
-  return t.data_ptr<double>();
-}
-
 bool integer_map(const Tensor& t) {
   const auto st = t.scalar_type();
   return st == at::kByte || st == at::kChar || st == at::kShort || st == at::kInt || st == at::kLong;
@@ -90,9 +84,9 @@ void segmentation_update(const Tensor& input, const Tensor& target, int64_t num_
   Tensor in, tg;
   tea::SegmentationArgs a =
       segmentation_args(input, target, num_classes, arm, ignore_index, err, in, tg, "segmentation_update");
-  a.dst[0] = class_state(intersection, input, num_classes, "segmentation_update", "intersection");
-  a.dst[1] = class_state(pred_count, input, num_classes, "segmentation_update", "pred_count");
-  a.dst[2] = class_state(target_count, input, num_classes, "segmentation_update", "target_count");
+  a.dst[0] = f64_buf(intersection, input, num_classes, "segmentation_update", "intersection");
+  a.dst[1] = f64_buf(pred_count, input, num_classes, "segmentation_update", "pred_count");
+  a.dst[2] = f64_buf(target_count, input, num_classes, "segmentation_update", "target_count");
   a.accumulate = 1;
   if (a.n == 0 || a.p == 0) return;
   DeviceGuard guard(input.device());
@@ -128,9 +122,9 @@ void segmentation_value(const Tensor& intersection, const Tensor& pred_count, co
   const int64_t c = intersection.numel();
   TORCH_CHECK(c >= 1, "segmentation_value: at least one class");
   TORCH_CHECK(average >= 0 && average <= 2, "segmentation_value: average must be 0 (macro), 1 (micro) or 2 (none)");
-  const double* i = class_state(intersection, intersection, c, "segmentation_value", "intersection");
-  const double* p = class_state(pred_count, intersection, c, "segmentation_value", "pred_count");
-  const double* t = class_state(target_count, intersection, c, "segmentation_value", "target_count");
+  const double* i = f64_buf(intersection, intersection, c, "segmentation_value", "intersection");
+  const double* p = f64_buf(pred_count, intersection, c, "segmentation_value", "pred_count");
+  const double* t = f64_buf(target_count, intersection, c, "segmentation_value", "target_count");
   float* o = f32_out(out, intersection, average == 2 ? c : 1, "out");
   DeviceGuard guard(intersection.device());
   check_launch(tea::launch_segmentation_value(i, p, t, c, dice ? 1 : 0, static_cast<int>(average), o,

@@ -214,6 +214,23 @@ __device__ __forceinline__ bool wt_arrive_last(unsigned* ticket, unsigned expect
 // launch and stream-ordered launches keep the sums deterministic.
 __device__ __forceinline__ void pend_add(double* p, double v) { unsafeAtomicAdd(p, v); }
 
+// ------------------------------------------------------------------ tiled kernels
+// tile t of the upper triangle (ti <= tj) of T x T tiles, enumerated row by row
+__device__ __forceinline__ void upper_tile_coords(int t, int T, int& ti, int& tj) {
+  int row = 0, rem = t;
+  while (rem >= T - row) {
+    rem -= T - row;
+    ++row;
+  }
+  ti = row;
+  tj = row + rem;
+}
+
+// every row of a float32 matrix starts on a 16-byte boundary (row stride in elements)
+inline bool rows_aligned16(const float* base, int64_t row_stride) {
+  return reinterpret_cast<uintptr_t>(base) % 16 == 0 && row_stride % 4 == 0;
+}
+
 // Grid sizing for streaming kernels: enough waves to fill 256 CUs, capped (Guideline 11).
 inline int stream_grid(int64_t work_items, int items_per_block, int cap) {
   int64_t g = (work_items + items_per_block - 1) / items_per_block;

@@ -53,6 +53,26 @@ inline float* f32_out(const optional<Tensor>& t, const Tensor& ref, int64_t nume
   return x.data_ptr<float>();
 }
 
+// float32 [n >= 1, D >= 1] features with unit stride along D (K20, K22)
+inline void check_features(const Tensor& t, const char* what, const char* name) {
+  check_gpu(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) >= 1 && t.size(1) >= 1 &&
+                  (t.stride(1) == 1 || t.size(1) == 1) && t.stride(0) >= 0,
+              what, ": ", name, " must be a float32 [n, D] tensor with unit stride along D");
+}
+
+// the data of a contiguous tensor of `dtype` with `numel` elements on `ref`'s device
+inline void* dense_buf(const Tensor& t, at::ScalarType dtype, const Tensor& ref, int64_t numel, const char* what,
+                       const char* name) {
+  TORCH_CHECK(t.scalar_type() == dtype && t.is_contiguous() && t.numel() == numel && t.device() == ref.device(),
+              what, ": ", name, " must be a contiguous ", dtype, " tensor of ", numel,
+              " elements on the inputs' device");
+  return t.data_ptr();
+}
+inline double* f64_buf(const Tensor& t, const Tensor& ref, int64_t numel, const char* what, const char* name) {
+  return static_cast<double*>(dense_buf(t, at::kDouble, ref, numel, what, name));
+}
+
 inline void check_launch(int rc, const char* what) {
   TORCH_CHECK(rc == 0, "torcheval_amd._C: ", what, " launch failed (code ", rc, ")");
 }

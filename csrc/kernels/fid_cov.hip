@@ -117,17 +117,6 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const
 // the per-lane SOURCE address instead.
 __device__ __forceinline__ int rot(int r) { return (r & 1) * 16 + ((r >> 1) & 1) * 32; }
 
-__device__ __forceinline__ void tile_coords(int t, int T, int& ti, int& tj) {
-  // t enumerates the upper triangle (ti <= tj) row by row
-  int row = 0, rem = t;
-  while (rem >= T - row) {
-    rem -= T - row;
-    ++row;
-  }
-  ti = row;
-  tj = row + rem;
-}
-
 // kMode 1 and 2: the products run on bf16 MFMA through the exact three-way split (split3) - six
 // products per operand pair (x1y1, x1y2, x2y1, x2y2, x1y3, x3y1; the dropped x2y3, x3y2, x3y3
 // are below 2^-23 |xy|), i.e. FP32-level products at 6/16 of the FP32 MFMA pipe time.
@@ -147,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void fid_syrk_kernel(FidCovArgs a, int T,
   if (item >= items) return;  // grid padding (whole block: no barrier is skipped halfway)
   const int ks = item / tiles, tile = item % tiles;
   int ti, tj;
-  tile_coords(tile, T, ti, tj);
+  upper_tile_coords(tile, T, ti, tj);
   const int64_t I0 = static_cast<int64_t>(ti) * kT, J0 = static_cast<int64_t>(tj) * kT;
   const bool diag = ti == tj;
   const int64_t k0 = ks * chunk;
@@ -628,7 +617,7 @@ __global__ __launch_bounds__(kFixThreads) void fid_fixup_kernel(FidCovArgs a, in
   const int sub = blockIdx.x % (kSub * kSub);
   const int r0 = (sub / kSub) * kS, c0 = (sub % kSub) * kS;
   int ti, tj;
-  tile_coords(tile, T, ti, tj);
+  upper_tile_coords(tile, T, ti, tj);
   const int64_t I0 = static_cast<int64_t>(ti) * kT, J0 = static_cast<int64_t>(tj) * kT;
   const bool diag = ti == tj;
   const int64_t items = static_cast<int64_t>(tiles) * a.split;

@@ -8,24 +8,16 @@
 // about a dozen passes over them.  Here everything after the dot product happens in the registers
 // that hold the Gram tile, so neither the Gram matrices nor the gathered rows ever exist.
 //
-// kid_gram_kernel, gfx950 mapping (the only arm):
+// kid_gram_kernel, gfx950 mapping (the only arm; the tile itself is tea_gramtile.h's):
 //  * one block = one 128 x 128 tile of one Gram block of one subset.  With T = ceil(m / 128) a
 //    subset has T (T + 1) / 2 upper-triangle tiles of XX, as many of YY and T^2 tiles of XY, in
 //    that order, each row-major.  The grid is padded to a multiple of 8 and block b takes item
 //    (b % 8) * (nb / 8) + b / 8 (K8's order), so an XCD owns a contiguous run of items that share a
 //    subset and a row panel in its L2.
-//  * the contraction runs over the contiguous dimension D, stepped by 32.  Four waves; wave w owns
-//    the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2 blocks of v_mfma_f32_32x32x2_f32: exact FP32
-//    products, a k-ordered fmaf chain per element, 64 accumulator registers.
-//  * staging: rows are fetched through the index lists.  Eight consecutive lanes read one row's
-//    128 bytes of the k-step with one 16-byte load each (row addresses 16-byte aligned), or with
-//    four element loads (any other base, row stride or D: correct, not tuned).  The next step's
-//    loads are issued into registers before this step's MFMAs and stored to LDS after them.  The
-//    K tail past D and the rows past m stage zeros.  Every index is clamped on the unsigned
-//    compare to n - 1 before it forms an address.
-//  * LDS image [k][row] with a row pitch of 130 floats: an operand read is 32 consecutive floats
-//    per half-wave, and the four k of a staged 16-byte piece land 8 banks apart per lane group
-//    (4 * 130 = 8 mod 32), so a wave's 64 stores spread over all 32 banks.
+//  * rows are fetched through the index lists; the rows past m stage zeros.  Every index is
+//    clamped on the unsigned compare to n - 1 before it forms an address.  One FP32 chain over all
+//    of D: the next stage's loads are issued into registers before this stage's MFMAs and stored
+//    to LDS after them.
 //  * epilogue in registers: each accumulator element is widened to FP64, v = fma(d, gamma, coef),
 //    the power by left-to-right repeated multiplication, then the mask: padding rows and columns
 //    are dropped (with coef != 0 they would add coef^degree each), i == j is dropped on the
@@ -40,32 +32,17 @@
 #include <algorithm>
 
 #include "tea_common.h"
+#include "tea_gramtile.h"
 #include "tea_kernels.h"
 
 namespace tea {
 
 namespace {
 
-constexpr int kT = kKidTile;   // 128
-constexpr int kBK = 32;        // k per stage
-constexpr int kThreads = 256;  // 4 waves
-constexpr int kPitch = kT + 2; // floats between two k rows of the LDS image
-constexpr int kPieces = kT * kBK / 4 / kThreads;  // 16-byte pieces per thread per operand (4)
+using namespace gramtile;
+
 constexpr int kFinishThreads = 1024;
-static_assert(kPieces * 32 == kT, "a thread's pieces are 32 rows apart");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// t enumerates the upper triangle (ti <= tj) row by row
-__device__ __forceinline__ void upper_coords(int t, int T, int& ti, int& tj) {
-  int row = 0, rem = t;
-  while (rem >= T - row) {
-    rem -= T - row;
-    ++row;
-  }
-  ti = row;
-  tj = row + rem;
-}
+static_assert(kKidTile == kT, "the tile is tea_gramtile.h's");
 
 __device__ __forceinline__ int64_t clamp_index(int32_t i, int64_t n) {
   const uint32_t u = static_cast<uint32_t>(i);  // a negative index compares as a large one
@@ -86,7 +63,7 @@ __global__ __launch_bounds__(kThreads) void kid_gram_kernel(KidGramArgs a, int T
   const bool rows_fake = item >= tri && sym;  // YY
   const bool cols_fake = item >= tri;          // YY and XY
   if (sym) {
-    upper_coords(item < tri ? item : item - tri, T, ti, tj);
+    upper_tile_coords(item < tri ? item : item - tri, T, ti, tj);
   } else {
     ti = (item - 2 * tri) / T;
     tj = (item - 2 * tri) % T;
@@ -94,99 +71,49 @@ __global__ __launch_bounds__(kThreads) void kid_gram_kernel(KidGramArgs a, int T
   const int m = static_cast<int>(a.m);
   const int d = static_cast<int>(a.d);
 
-  __shared__ __attribute__((aligned(16))) float sA[kBK * kPitch];
-  __shared__ __attribute__((aligned(16))) float sB[kBK * kPitch];
+  __shared__ __attribute__((aligned(16))) float sA[kImage];
+  __shared__ __attribute__((aligned(16))) float sB[kImage];
   __shared__ double s_wave[kThreads / kWave];
 
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int wr = w >> 1, wc = w & 1;
 
-  // ---- staging: piece q of thread t is row (t >> 3) + 32 q, k [4 (t & 7), + 4) of the stage
-  const int rslot = threadIdx.x >> 3, kq = threadIdx.x & 7;
-  const float* pa[kPieces];
-  const float* pb[kPieces];
+  // ---- staging: the thread's rows of both operands, through the index lists
+  Stage st;
+  st.rslot = threadIdx.x >> 3;
+  st.kq = threadIdx.x & 7;
+  st.d = d;
 #pragma unroll
   for (int q = 0; q < kPieces; ++q) {
-    const int r = rslot + 32 * q;
+    const int r = st.rslot + 32 * q;
     const int gi = ti * kT + r, gj = tj * kT + r;
-    pa[q] = nullptr;
-    pb[q] = nullptr;
+    st.pa[q] = nullptr;
+    st.pb[q] = nullptr;
     if (gi < m) {
-      pa[q] = rows_fake ? a.fake + clamp_index(a.idx_f[s * a.m + gi], a.n_f) * a.fake_stride
-                        : a.real + clamp_index(a.idx_r[s * a.m + gi], a.n_r) * a.real_stride;
+      st.pa[q] = rows_fake ? a.fake + clamp_index(a.idx_f[s * a.m + gi], a.n_f) * a.fake_stride
+                           : a.real + clamp_index(a.idx_r[s * a.m + gi], a.n_r) * a.real_stride;
     }
     if (gj < m) {
-      pb[q] = cols_fake ? a.fake + clamp_index(a.idx_f[s * a.m + gj], a.n_f) * a.fake_stride
-                        : a.real + clamp_index(a.idx_r[s * a.m + gj], a.n_r) * a.real_stride;
+      st.pb[q] = cols_fake ? a.fake + clamp_index(a.idx_f[s * a.m + gj], a.n_f) * a.fake_stride
+                           : a.real + clamp_index(a.idx_r[s * a.m + gj], a.n_r) * a.real_stride;
     }
   }
-  float4 va[kPieces], vb[kPieces];
-  auto fetch = [&](const float* p, int col) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (p == nullptr) return v;
-    if constexpr (kVec) {
-      if (col < d) v = *reinterpret_cast<const float4*>(p + col);  // d % 4 == 0: wholly inside
-    } else {
-      if (col < d) v.x = p[col];
-      if (col + 1 < d) v.y = p[col + 1];
-      if (col + 2 < d) v.z = p[col + 2];
-      if (col + 3 < d) v.w = p[col + 3];
-    }
-    return v;
-  };
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < kPieces; ++q) {
-      va[q] = fetch(pa[q], k0 + 4 * kq);
-      vb[q] = fetch(pb[q], k0 + 4 * kq);
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int q = 0; q < kPieces; ++q) {
-      const int o = 4 * kq * kPitch + rslot + 32 * q;
-      sA[o] = va[q].x;
-      sA[o + kPitch] = va[q].y;
-      sA[o + 2 * kPitch] = va[q].z;
-      sA[o + 3 * kPitch] = va[q].w;
-      sB[o] = vb[q].x;
-      sB[o + kPitch] = vb[q].y;
-      sB[o + 2 * kPitch] = vb[q].z;
-      sB[o + 3 * kPitch] = vb[q].w;
-    }
-  };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-    for (int bn = 0; bn < 2; ++bn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[bm][bn][r] = 0.f;
+  zero(acc);
+  const int offA = operand_offset(lane, wr), offB = operand_offset(lane, wc);
 
-  // operand lane map of v_mfma_f32_32x32x2_f32: A[i = lane & 31][k = lane >> 5], B[k][j = lane & 31]
-  const int offA = (lane >> 5) * kPitch + wr * 64 + (lane & 31);
-  const int offB = (lane >> 5) * kPitch + wc * 64 + (lane & 31);
-
-  load(0);
+  st.load<kVec>(0);
   for (int k0 = 0; k0 < d; k0 += kBK) {
-    store();
+    st.store(sA, sB);
     __syncthreads();
-    if (k0 + kBK < d) load(k0 + kBK);  // in flight behind this stage's MFMAs
-#pragma unroll
-    for (int kk = 0; kk < kBK / 2; ++kk) {
-      const float a0 = sA[2 * kk * kPitch + offA], a1 = sA[2 * kk * kPitch + offA + 32];
-      const float b0 = sB[2 * kk * kPitch + offB], b1 = sB[2 * kk * kPitch + offB + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    if (k0 + kBK < d) st.load<kVec>(k0 + kBK);  // in flight behind this stage's MFMAs
+    mfma_stage(sA, sB, offA, offB, acc);
     __syncthreads();
   }
 
-  // ---- epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // ---- epilogue
   const bool diag = sym && ti == tj;
   double sum = 0.0;
 #pragma unroll
@@ -197,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void kid_gram_kernel(KidGramArgs a, int T
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
 #pragma clang fp contract(off)  // the power is a chain of rounded FP64 products (the definition)
-        const int i = ti * kT + wr * 64 + bm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int i = ti * kT + wr * 64 + bm * 32 + cd_row(r, lane);
         const double v = fma(static_cast<double>(acc[bm][bn][r]), a.gamma, a.coef);
         double p = v;
         for (int e = 1; e < a.degree; ++e) p *= v;
@@ -258,12 +185,10 @@ __global__ __launch_bounds__(kFinishThreads) void kid_finish_kernel(KidFinishArg
   }
 }
 
-int tiles_of(int64_t m) { return static_cast<int>((m + kT - 1) / kT); }
-
 }  // namespace
 
 int64_t kid_items(int64_t m) {
-  const int64_t T = (m + kT - 1) / kT;
+  const int64_t T = tiles_of(m);
   return T * (T + 1) + T * T;
 }
 
@@ -276,9 +201,8 @@ int launch_kid_gram(const KidGramArgs& a, hipStream_t stream) {
   const int64_t total = a.subsets * items;
   const int64_t grid = (total + 7) / 8 * 8;
   if (grid >= (int64_t{1} << 31)) return -1;
-  const bool vec = a.d % 4 == 0 && a.real_stride % 4 == 0 && a.fake_stride % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(a.real) % 16 == 0 && reinterpret_cast<uintptr_t>(a.fake) % 16 == 0;
-  const int T = tiles_of(a.m);
+  const bool vec = a.d % 4 == 0 && rows_aligned16(a.real, a.real_stride) && rows_aligned16(a.fake, a.fake_stride);
+  const int T = static_cast<int>(tiles_of(a.m));
   if (vec)
     hipLaunchKernelGGL(kid_gram_kernel<true>, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, stream, a, T,
                        static_cast<int>(items), total);
@@ -290,7 +214,7 @@ int launch_kid_gram(const KidGramArgs& a, hipStream_t stream) {
 
 int launch_kid_finish(const KidFinishArgs& a, hipStream_t stream) {
   if (a.subsets < 1 || a.m < 2 || a.m >= (int64_t{1} << 24) || kid_items(a.m) >= (int64_t{1} << 31)) return -1;
-  hipLaunchKernelGGL(kid_finish_kernel, dim3(1), dim3(kFinishThreads), 0, stream, a, tiles_of(a.m),
+  hipLaunchKernelGGL(kid_finish_kernel, dim3(1), dim3(kFinishThreads), 0, stream, a, static_cast<int>(tiles_of(a.m)),
                      static_cast<int>(kid_items(a.m)));
   return static_cast<int>(hipGetLastError());
 }

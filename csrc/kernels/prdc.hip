@@ -14,15 +14,12 @@
 // float32 is exact in FP64); lane l takes the columns 4 l .. 4 l + 3 (+ 256 per step) in both load
 // arms, so the arms add in one order.
 //
-// prdc_tile_kernel<Mode, kVec>, gfx950 mapping (the only arm):
+// prdc_tile_kernel<Mode, kVec>, gfx950 mapping (the only arm; the tile itself is tea_gramtile.h's):
 //  * block (p, g) owns the 128-row panel p of the query set and walks the column tiles g, g + G, ...
-//    of the reference set (G = PrdcTileArgs::groups, rule at prdc_groups).  Per tile it runs K20's
-//    main loop: the contraction over the contiguous dimension D stepped by 32, four waves, wave w
-//    owning the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2 blocks of v_mfma_f32_32x32x2_f32, the
-//    [k][row] LDS image at a pitch of 130 floats, the next stage's loads issued before this stage's
-//    MFMAs, zeros staged for the K tail, the rows past n_q and the columns past n_ref, 16-byte loads
-//    when every row address is 16-byte aligned (kVec) and four element loads otherwise.  Rows are
-//    addressed directly.  Unlike K20 the inner product is not one chain: a selection compares single
+//    of the reference set (G = PrdcTileArgs::groups, rule at prdc_groups).  Rows are addressed
+//    directly; the rows past n_q and the columns past n_ref stage zeros.  The next stage's loads are
+//    issued before this stage's MFMAs.
+//  * unlike K20 the inner product is not one chain: a selection compares single
 //    distances, where K20 adds thousands, and one k-ordered float32 fmaf chain over D = 2048
 //    non-negative features is off by up to 2.6e-6 of sum |a_k| |b_k| (its partial sum grows with k
 //    and every step rounds at its size).  The MFMAs therefore run a chain per 128 k (four stages) in
@@ -59,6 +56,7 @@
 #include <algorithm>
 
 #include "tea_common.h"
+#include "tea_gramtile.h"
 #include "tea_kernels.h"
 #include "tea_partials.h"
 
@@ -66,20 +64,15 @@ namespace tea {
 
 namespace {
 
-constexpr int kT = kPrdcTile;  // 128
-constexpr int kBK = 32;        // k per stage
+using namespace gramtile;
+
 constexpr int kChunk = 128;    // k per MFMA chain: four stages, then the chain's sum joins the accumulator
-constexpr int kThreads = 256;  // 4 waves
-constexpr int kPitch = kT + 2; // floats between two k rows of the LDS image
-constexpr int kPieces = kT * kBK / 4 / kThreads;  // 16-byte pieces per thread per operand (4)
 constexpr int kWaves = kThreads / kWave;
 constexpr int kWaveRows = 64;  // rows (and columns) of a wave's quadrant
 constexpr int kRadiiThreads = 256;
-static_assert(kPieces * 32 == kT, "a thread's pieces are 32 rows apart");
+static_assert(kPrdcTile == kT, "the tile is tea_gramtile.h's");
 static_assert(kWaves * kWaveRows == 2 * kT, "four quadrants of 64 x 64");
-static_assert(2 * 32 * kWave <= kBK * kPitch, "two waves' epilogue halves fit one operand's staging image");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+static_assert(2 * 32 * kWave <= kImage, "two waves' epilogue halves fit one operand's staging image");
 
 enum class Mode { Knn, Cross };
 
@@ -130,8 +123,8 @@ __global__ __launch_bounds__(kThreads, 2) void prdc_tile_kernel(PrdcTileArgs a, 
   const int d = static_cast<int>(a.d);
   const int k = a.k;
 
-  __shared__ __attribute__((aligned(16))) float sA[kBK * kPitch];
-  __shared__ __attribute__((aligned(16))) float sB[kBK * kPitch];
+  __shared__ __attribute__((aligned(16))) float sA[kImage];
+  __shared__ __attribute__((aligned(16))) float sB[kImage];
   __shared__ double s_norm[kT];                                               // the panel's row norms
   __shared__ double s_top[kKnn ? kWaves * kWaveRows * kPrdcMaxK : 1];         // Knn: [wave][row][slot]
   __shared__ double s_min[kKnn ? 1 : kWaves * kWaveRows];                     // Cross: [wave][row]
@@ -155,95 +148,40 @@ __global__ __launch_bounds__(kThreads, 2) void prdc_tile_kernel(PrdcTileArgs a, 
   }
   // the main loop's barriers order these stores before the first epilogue
 
-  // ---- staging: piece q of thread t is row (t >> 3) + 32 q, k [4 (t & 7), + 4) of the stage
-  const int rslot = threadIdx.x >> 3, kq = threadIdx.x & 7;
-  const float* pa[kPieces];
-  const float* pb[kPieces];
+  // ---- staging: the thread's rows of the panel; those of a column tile at first_stage
+  Stage st;
+  st.rslot = threadIdx.x >> 3;
+  st.kq = threadIdx.x & 7;
+  st.d = d;
 #pragma unroll
   for (int q = 0; q < kPieces; ++q) {
-    const int gi = p * kT + rslot + 32 * q;
-    pa[q] = gi < n_q ? a.query + static_cast<int64_t>(gi) * a.query_stride : nullptr;
+    const int gi = p * kT + st.rslot + 32 * q;
+    st.pa[q] = gi < n_q ? a.query + static_cast<int64_t>(gi) * a.query_stride : nullptr;
   }
-  float4 va[kPieces], vb[kPieces];
-  auto fetch = [&](const float* ptr, int col) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ptr == nullptr) return v;
-    if constexpr (kVec) {
-      if (col < d) v = *reinterpret_cast<const float4*>(ptr + col);  // d % 4 == 0: wholly inside
-    } else {
-      if (col < d) v.x = ptr[col];
-      if (col + 1 < d) v.y = ptr[col + 1];
-      if (col + 2 < d) v.z = ptr[col + 2];
-      if (col + 3 < d) v.w = ptr[col + 3];
-    }
-    return v;
-  };
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < kPieces; ++q) {
-      va[q] = fetch(pa[q], k0 + 4 * kq);
-      vb[q] = fetch(pb[q], k0 + 4 * kq);
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int q = 0; q < kPieces; ++q) {
-      const int o = 4 * kq * kPitch + rslot + 32 * q;
-      sA[o] = va[q].x;
-      sA[o + kPitch] = va[q].y;
-      sA[o + 2 * kPitch] = va[q].z;
-      sA[o + 3 * kPitch] = va[q].w;
-      sB[o] = vb[q].x;
-      sB[o + kPitch] = vb[q].y;
-      sB[o + 2 * kPitch] = vb[q].z;
-      sB[o + 3 * kPitch] = vb[q].w;
-    }
-  };
-
-  // operand lane map of v_mfma_f32_32x32x2_f32: A[i = lane & 31][k = lane >> 5], B[k][j = lane & 31]
-  const int offA = (lane >> 5) * kPitch + wr * 64 + (lane & 31);
-  const int offB = (lane >> 5) * kPitch + wc * 64 + (lane & 31);
+  const int offA = operand_offset(lane, wr), offB = operand_offset(lane, wc);
 
   auto first_stage = [&](int tj) {  // the tile's column rows, and its first stage into registers
 #pragma unroll
     for (int q = 0; q < kPieces; ++q) {
-      const int gj = tj * kT + rslot + 32 * q;
-      pb[q] = gj < n_ref ? a.ref + static_cast<int64_t>(gj) * a.ref_stride : nullptr;
+      const int gj = tj * kT + st.rslot + 32 * q;
+      st.pb[q] = gj < n_ref ? a.ref + static_cast<int64_t>(gj) * a.ref_stride : nullptr;
     }
-    load(0);
+    st.load<kVec>(0);
   };
   first_stage(g);
   for (int tj = g; tj < col_tiles; tj += G) {
     f32x16 acc[2][2];  // the float32 sum, in k order, of the finished chunks' chains
-#pragma unroll
-    for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-      for (int bn = 0; bn < 2; ++bn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[bm][bn][r] = 0.f;
+    zero(acc);
 
     for (int kc = 0; kc < d; kc += kChunk) {
       f32x16 part[2][2];  // the MFMA chain of this chunk of k
-#pragma unroll
-      for (int bm = 0; bm < 2; ++bm)
-#pragma unroll
-        for (int bn = 0; bn < 2; ++bn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) part[bm][bn][r] = 0.f;
+      zero(part);
       const int kend = min(kc + kChunk, d);
       for (int k0 = kc; k0 < kend; k0 += kBK) {
-        store();
+        st.store(sA, sB);
         __syncthreads();
-        if (k0 + kBK < d) load(k0 + kBK);  // in flight behind this stage's MFMAs
-#pragma unroll
-        for (int kk = 0; kk < kBK / 2; ++kk) {
-          const float a0 = sA[2 * kk * kPitch + offA], a1 = sA[2 * kk * kPitch + offA + 32];
-          const float b0 = sB[2 * kk * kPitch + offB], b1 = sB[2 * kk * kPitch + offB + 32];
-          part[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, part[0][0], 0, 0, 0);
-          part[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, part[0][1], 0, 0, 0);
-          part[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, part[1][0], 0, 0, 0);
-          part[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, part[1][1], 0, 0, 0);
-        }
+        if (k0 + kBK < d) st.load<kVec>(k0 + kBK);  // in flight behind this stage's MFMAs
+        mfma_stage(sA, sB, offA, offB, part);
         __syncthreads();
       }
 #pragma unroll
@@ -254,7 +192,7 @@ __global__ __launch_bounds__(kThreads, 2) void prdc_tile_kernel(PrdcTileArgs a, 
 
     if (tj + G < col_tiles) first_stage(tj + G);  // the next tile's loads fly behind the epilogue
 
-    // ---- epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // ---- epilogue
     const int c0 = tj * kT + wc * 64 + j, c1 = c0 + 32;
     const bool in0 = c0 < n_ref, in1 = c1 < n_ref;
     const double nb0 = in0 ? a.norms_ref[c0] : 0.0, nb1 = in1 ? a.norms_ref[c1] : 0.0;
@@ -277,7 +215,7 @@ __global__ __launch_bounds__(kThreads, 2) void prdc_tile_kernel(PrdcTileArgs a, 
       }
 #pragma unroll 1
       for (int r = 0; r < 16; ++r) {
-        const int rl = bm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;  // row of the wave's 64
+        const int rl = bm * 32 + cd_row(r, lane);  // row of the wave's 64
         const double na = s_norm[wr * 64 + rl];
         double e0 = fmax(0.0, (na + nb0) - 2.0 * static_cast<double>(stage[(2 * r) * kWave]));
         double e1 = fmax(0.0, (na + nb1) - 2.0 * static_cast<double>(stage[(2 * r + 1) * kWave]));
@@ -415,10 +353,6 @@ __global__ __launch_bounds__(kWave) void prdc_finish_kernel(PrdcFinishArgs a, in
   a.values[3] = static_cast<float>(static_cast<double>(t[3]) / n_r);
 }
 
-int64_t tiles_of(int64_t n) { return (n + kT - 1) / kT; }
-
-bool aligned16(const float* p, int64_t stride) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && stride % 4 == 0; }
-
 bool tile_args_ok(const PrdcTileArgs& a) {
   if (a.n_q < 1 || a.n_ref < 1 || a.d < 1 || a.groups < 1 || a.groups > tiles_of(a.n_ref)) return false;
   if (a.n_q >= (int64_t{1} << 31) - kT || a.n_ref >= (int64_t{1} << 31) - kT || a.d >= (int64_t{1} << 31) - kBK)
@@ -428,7 +362,7 @@ bool tile_args_ok(const PrdcTileArgs& a) {
 
 template <Mode kMode>
 int launch_tile(const PrdcTileArgs& a, hipStream_t stream) {
-  const bool vec = a.d % 4 == 0 && aligned16(a.query, a.query_stride) && aligned16(a.ref, a.ref_stride);
+  const bool vec = a.d % 4 == 0 && rows_aligned16(a.query, a.query_stride) && rows_aligned16(a.ref, a.ref_stride);
   const dim3 grid(static_cast<unsigned>(tiles_of(a.n_q) * a.groups));
   const int col_tiles = static_cast<int>(tiles_of(a.n_ref));
   if (vec)
@@ -463,7 +397,7 @@ int64_t prdc_hits_blocks(int64_t n_r, int64_t n_f) {
 
 int launch_prdc_norms(const PrdcNormsArgs& a, hipStream_t stream) {
   if (a.n_r < 1 || a.n_f < 1 || a.d < 1 || a.d >= (int64_t{1} << 31) || a.n_r + a.n_f >= (int64_t{1} << 32)) return -1;
-  const bool vec = a.d % 4 == 0 && aligned16(a.real, a.real_stride) && aligned16(a.fake, a.fake_stride);
+  const bool vec = a.d % 4 == 0 && rows_aligned16(a.real, a.real_stride) && rows_aligned16(a.fake, a.fake_stride);
   const dim3 grid(static_cast<unsigned>((a.n_r + a.n_f + kWaves - 1) / kWaves));
   if (vec)
     hipLaunchKernelGGL(prdc_norms_kernel<true>, grid, dim3(kThreads), 0, stream, a);

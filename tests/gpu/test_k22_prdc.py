@@ -111,6 +111,16 @@ def test_exact_at_every_tile_and_width_edge(k, d):
         check_exact(*integer_features(n, m, d, 1000 * n + m + d), k)
 
 
+@pytest.mark.parametrize("d", [129, 132, 160])
+def test_exact_where_a_stage_follows_a_chain_boundary(d):
+    """The MFMA chains are 128 k long (four stages of 32).  WIDTHS ends inside one chain (100) or on
+    a boundary (256); here a second chain holds a partial stage, through the element loads (129) and
+    the 16-byte loads (132), or exactly one full stage (160).  Dot products stay below
+    9 * 160 = 1440."""
+    for n, m in size_pairs(3):
+        check_exact(*integer_features(n, m, d, 1000 * n + m + d), 3)
+
+
 @pytest.mark.parametrize("k", [1, 5, 8])
 @pytest.mark.parametrize("d", [4, 64])
 def test_every_group_count_gives_the_same_lists(k, d):
