@@ -256,6 +256,17 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: (F.density_coverage if dc else F.improved_precision_recall)(real, fake)
         return make
 
+    def silhouette(cls, rows, d, k):
+        def make():
+            rows_ = rows if s >= 1 else n(rows // 40)
+            labels = randint(k, rows_)
+            x = rand(k, d)[labels] + 0.35 * rand(rows_, d)
+            if cls:
+                metric = M.SilhouetteScore(num_clusters=k, device=dev).update(x, labels)
+                return lambda: metric.compute()
+            return lambda: F.silhouette_score(x, labels, num_clusters=k)
+        return make
+
     def ndcg(cls):
         def make():
             x, t = rand(B, C), randint(5, B, C)
@@ -492,6 +503,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "improved_precision_recall 10000x2048, k=3 (K22)": prdc(False, False, 10000, 2048),
         "DensityCoverage.compute 10000x2048, k=5 (K22)": prdc(True, True, 10000, 2048),
         "density_coverage 10000x64, k=5 (K22)": prdc(False, True, 10000, 64),
+        "silhouette_score 10000x64, 10 clusters (K23)": silhouette(False, 10000, 64, 10),
+        "SilhouetteScore.compute 10000x2048, 10 clusters (K23)": silhouette(True, 10000, 2048, 10),
         "inception_score 8192x1000, 10 splits (K21)": inception(False),
         "InceptionScore.update_logits+compute 8192x1000, 10 splits (K21)": inception(True),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),

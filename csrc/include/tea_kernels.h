@@ -1015,3 +1015,54 @@ int launch_prdc_radii(const double* partial, int64_t n, int lists, int k, double
 int64_t prdc_hits_blocks(int64_t n_r, int64_t n_f);
 int launch_prdc_finish(const PrdcFinishArgs& a, hipStream_t stream);  // two launches
 }  // namespace tea
+
+namespace tea {
+// K23: silhouette coefficient (csrc/kernels/silhouette.hip; docs/parity.md, "Not in the reference").
+// With d(i, j) the Euclidean distance, a(i) is the mean of d over the other members of i's cluster,
+// b(i) the smallest mean of d over another non-empty cluster and s(i) = (b - a) / max(a, b).
+// silhouette_tile_kernel walks 128 x 128 FP32-MFMA tiles of <x_r, x_i> (K22's main loop) whose rows
+// are 128-row panels of one cluster each (the samples sorted by cluster, every cluster padded to
+// whole panels) and whose columns are the query samples; a lane adds its columns' distances over
+// the rows in FP64, so neither a distance nor a per-cluster table is ever written to memory.
+constexpr int kSilTile = 128;          // rows of a panel, columns of a column tile
+constexpr int kSilCUs = 256;           // compute units of the MI355X, which the group rule balances over
+constexpr int kSilMaxGroups = 16;      // the rule's largest G
+constexpr int kSilBlockStages = 12;    // a block's fixed cost in the rule, in 32-wide k-steps of one tile
+constexpr int kSilEpilogueStages = 6;  // a tile's epilogue (128 FP64 square roots per lane), in k-steps
+constexpr int kSilStitchRows = 256;    // samples per block of silhouette_stitch_kernel
+// Panel groups G of a call with n samples of width d and at most max_panels panels: block (q, g)
+// owns column tile q and walks the panels [g T / G, (g + 1) T / G) of the T <= max_panels panels the
+// device counted.  `groups` >= 1 is taken as given (clamped to max_panels).  0 is the rule, K22's
+// with the epilogue added to a tile: the G in 1 .. min(max_panels, kSilMaxGroups) with the smallest
+//   c (t (ceil(d / 32) + kSilEpilogueStages) + kSilBlockStages) (c == 1 ? 4 : 3),
+//   c = ceil(column tiles G / kSilCUs),  t = ceil(max_panels / G)
+// (the smallest such G on a tie).  A model: nothing of it has been fitted to this kernel yet.
+int64_t silhouette_groups(int64_t n, int64_t max_panels, int64_t d, int64_t groups);
+int64_t silhouette_stitch_blocks(int64_t n);
+struct SilhouetteArgs {
+  const float* x = nullptr;              // [n, D], unit stride along D
+  int64_t stride = 0;                    // row stride in elements
+  int64_t n = 0;
+  int64_t d = 0;
+  double* norms = nullptr;               // [n]: FP64 sums of squares, NaN for a row with a NaN or inf
+  const int32_t* labels = nullptr;       // [n]: cluster of a sample, -1 for a label outside [0, k)
+  const int32_t* ref_index = nullptr;    // [max_panels * 128]: sample of a panel row, -1 for padding
+  const int32_t* panel_cluster = nullptr;  // [max_panels]: cluster of a panel, -1 past the last
+  const int32_t* counts = nullptr;       // [k]: members per cluster
+  const int32_t* num_panels = nullptr;   // [1]: T, on the device
+  int max_panels = 0;
+  int k = 0;
+  int groups = 0;                        // G >= 1 (silhouette_groups)
+  double* edges = nullptr;               // [G, 4, n]: first sum, last sum, inside minimum, inside own sum
+  double* a = nullptr;                   // [n]
+  double* b = nullptr;                   // [n]
+  double* s = nullptr;                   // [n]
+  float* samples = nullptr;              // [n]
+  double* block_sums = nullptr;          // [silhouette_stitch_blocks(n)] scratch
+  double* score64 = nullptr;             // [1]
+  float* score = nullptr;                // [1]
+};
+int launch_silhouette_norms(const SilhouetteArgs& a, hipStream_t stream);
+int launch_silhouette_tile(const SilhouetteArgs& a, hipStream_t stream);
+int launch_silhouette_finish(const SilhouetteArgs& a, hipStream_t stream);  // stitch and finish: two launches
+}  // namespace tea

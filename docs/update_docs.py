@@ -34,6 +34,7 @@ PAGES: Dict[str, Tuple[str, str, List[str]]] = {
             "torcheval_amd.metrics.metric",
             "torcheval_amd.metrics.aggregation",
             "torcheval_amd.metrics.classification",
+            "torcheval_amd.metrics.clustering",
             "torcheval_amd.metrics.image",
             "torcheval_amd.metrics.ranking",
             "torcheval_amd.metrics.regression",
@@ -47,6 +48,7 @@ PAGES: Dict[str, Tuple[str, str, List[str]]] = {
         [
             "torcheval_amd.metrics.functional.aggregation",
             "torcheval_amd.metrics.functional.classification",
+            "torcheval_amd.metrics.functional.clustering",
             "torcheval_amd.metrics.functional.image",
             "torcheval_amd.metrics.functional.ranking",
             "torcheval_amd.metrics.functional.regression",
