@@ -16,6 +16,10 @@
 // x_c < thr[b_true - 1], b_c == b_true <=> thr[b_true - 1] <= x_c < thr[b_true].  So one
 // binary search per SAMPLE (of its true score, in LDS), no per-class search, no histogram,
 // one streaming read of the scores.  NaN scores compare false (bin 0), as `>=` does there.
+// -inf is below every threshold (bin 0) and +inf at or above every one (bin T), so the top bin
+// has no upper edge: for b_true == T the "thr[b_true]" is a NaN sentinel and the test reads
+// !(x_c >= thr[b_true]), which equals x_c < thr[b_true] for every real edge and holds for every
+// score, +inf included, against the sentinel.
 //
 // Layout: G lanes per sample (G = the next power of two >= C / 4, at most 64), 16-B loads at
 // 4-B alignment (tea_common.h load_f4u; any width, any row stride); U = 8 samples per lane
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(kB) void sample_binned_auroc_kernel(SampleAurocArgs
     for (int u = 0; u < kU; ++u) {
       bt[u] = upper_bound_f32(thr, T, xt[u]);
       lo[u] = bt[u] >= 1 ? thr[bt[u] - 1] : __builtin_inff();
-      hi[u] = bt[u] < T ? thr[bt[u]] : __builtin_inff();
+      hi[u] = bt[u] < T ? thr[bt[u]] : __builtin_nanf("");  // the top bin: nothing is >= NaN
     }
     int less[kU], eq[kU], pos[kU];
 #pragma unroll
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(kB) void sample_binned_auroc_kernel(SampleAurocArgs
         const bool p = in && x >= t0;
         pos[u] += p;
         less[u] += p && x < lo[u];
-        eq[u] += in && x >= lo[u] && x < hi[u];
+        eq[u] += in && x >= lo[u] && !(x >= hi[u]);
       }
     };
     if constexpr (NARROW) {
@@ -128,7 +132,7 @@ __global__ __launch_bounds__(kB) void sample_binned_auroc_kernel(SampleAurocArgs
         const bool p = in && x >= t0;
         pos[u] += p;
         less[u] += p && x < lo[u];
-        eq[u] += in && x >= lo[u] && x < hi[u];
+        eq[u] += in && x >= lo[u] && !(x >= hi[u]);
       }
     } else {
 #pragma unroll
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(kB) void sample_binned_auroc_kernel(SampleAurocArgs
       }
       const int64_t s = s0 + static_cast<int64_t>(u) * ngroups;
       if (gl == 0 && s < a.n) {
-        // the true class sits in eq and pos (x_true >= thr[b - 1] >= thr_0, < thr[b])
+        // the true class sits in eq and pos (x_true >= thr[b - 1] >= thr_0, not >= thr[b])
         const int e = eq[u] - 1, p = pos[u] - 1;
         const float area = static_cast<float>(less[u]) + 0.5f * static_cast<float>(e);
         a.out[s] = (bt[u] >= 1 && p > 0) ? area / static_cast<float>(p) : 0.5f;

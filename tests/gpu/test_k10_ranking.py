@@ -20,10 +20,33 @@ def test_k10_matches_aten(n, c, dtype):
         x[1, 2] = float("nan")
         x[3].fill_(float("nan"))
     t = torch.randint(0, c, (n,), generator=g)
+    if n > 10 and c > 3:
+        inf = float("inf")
+        x[4, 0] = inf  # a candidate above every target score, or the target itself when t[4] == 0
+        x[5, t[5]] = inf  # an infinite target score: nothing ranks above it
+        x[6, t[6]] = -inf  # ... and one every finite candidate ranks above
+        x[7, 1] = -inf
+        x[8, t[8]] = x[8, (t[8] + 1) % c] = inf  # a tie at +inf does not count
+        x[9, t[9]] = x[9, (t[9] + 1) % c] = -inf
+        x[10].fill_(inf)
     for k in (None, 1, 3, c):
         if k is not None and k > 0:
             torch.testing.assert_close(hit_rate(x.cuda(), t.cuda(), k=k).cpu(), hit_rate(x, t, k=k))
         torch.testing.assert_close(reciprocal_rank(x.cuda(), t.cuda(), k=k).cpu(), reciprocal_rank(x, t, k=k))
+
+
+def test_k10_wide_kernel_past_one_grid_stride_trip():
+    """The wide kernel runs at most 16 384 blocks of 4 waves, one row per wave: 65 536 rows in the
+    first trip, so the last 4 of 65 540 rows take a second one."""
+    n, c = 16384 * 4 + 4, 64
+    g = torch.Generator().manual_seed(11)
+    x = torch.randint(0, 17, (n, c), generator=g).float() / 17
+    t = torch.randint(0, c, (n,), generator=g)
+    x[-1, t[-1]] = float("inf")
+    x[-2, t[-2]] = float("-inf")
+    xd, td = x.cuda(), t.cuda()
+    torch.testing.assert_close(reciprocal_rank(xd, td).cpu(), reciprocal_rank(x, t), rtol=0, atol=0)
+    torch.testing.assert_close(hit_rate(xd, td, k=3).cpu(), hit_rate(x, t, k=3), rtol=0, atol=0)
 
 
 def test_k10_strided_rows_and_int32_targets():
