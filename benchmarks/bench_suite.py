@@ -267,6 +267,21 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
             return lambda: F.silhouette_score(x, labels, num_clusters=k)
         return make
 
+    def detection_map(compute):
+        def make():
+            from benchmarks.bench_detection_map import batches, data
+
+            images = 5000 if s >= 1 else 8
+            packed = data(images, 100 if s >= 1 else 8, 80, dev)
+            metric = M.MeanAveragePrecision(80, device=dev)
+            if compute:
+                for batch in batches(packed, 32):
+                    metric.update_packed(*batch)
+                return lambda: metric.compute()
+            first = batches(packed, 32)[0]
+            return lambda: metric.update_packed(*first)
+        return make
+
     def ndcg(cls):
         def make():
             x, t = rand(B, C), randint(5, B, C)
@@ -505,6 +520,8 @@ def cases(dev: torch.device, s: float) -> Dict[str, Callable[[], Callable[[], ob
         "density_coverage 10000x64, k=5 (K22)": prdc(False, True, 10000, 64),
         "silhouette_score 10000x64, 10 clusters (K23)": silhouette(False, 10000, 64, 10),
         "SilhouetteScore.compute 10000x2048, 10 clusters (K23)": silhouette(True, 10000, 2048, 10),
+        "MeanAveragePrecision.update_packed 32 images x 100 detections, 80 classes (K24)": detection_map(False),
+        "MeanAveragePrecision.compute 5000 images x 100 detections, 80 classes (K24)": detection_map(True),
         "inception_score 8192x1000, 10 splits (K21)": inception(False),
         "InceptionScore.update_logits+compute 8192x1000, 10 splits (K21)": inception(True),
         "ClickThroughRate(64 tasks).update 8192x1000 (K5b)": k5b(M.ClickThroughRate, "ctr"),

@@ -1066,3 +1066,60 @@ int launch_silhouette_norms(const SilhouetteArgs& a, hipStream_t stream);
 int launch_silhouette_tile(const SilhouetteArgs& a, hipStream_t stream);
 int launch_silhouette_finish(const SilhouetteArgs& a, hipStream_t stream);  // stitch and finish: two launches
 }  // namespace tea
+
+namespace tea {
+// K24: COCO-style detection mean average precision (csrc/kernels/detection_map.hip; docs/parity.md,
+// "Not in the reference").  map_match_kernel: a workgroup per image (persistent grid) stages the
+// image's boxes in LDS, orders detections by (label, score descending, index) and ground truths by
+// (label, index) with an LDS bitonic sort, and its waves share the class segments: per kept
+// detection a wave forms the FP64 IoUs with the class's ground truths, 64 at a time, and per
+// threshold takes the unmatched ground truth of the largest IoU (the later among equals).
+// map_curve_kernel: a workgroup per (class, threshold) walks the class's hits from the right.
+constexpr int kMapMaxBoxes = 1024;      // detections, and ground truths, of one image (LDS: about 46 KB)
+constexpr int kMapBlock = 256;          // threads of a map_match workgroup
+constexpr int kMapGrid = 768;           // its largest grid: three workgroups per compute unit
+constexpr int kMapMaxThresholds = 16;   // bits of a ground truth's matched mask
+constexpr int kMapMaxClasses = 4194303;  // labels take 22 bits of the keys; 2^22 - 1 is "no class"
+constexpr int kMapCurveChunk = 256;     // positions of a map_curve step, one per thread
+constexpr int kMapCurveGrid = 4096;     // its largest grid
+// bits of the flag: a NaN score, a non-finite coordinate, x2 < x1 or y2 < y1, a label outside [0, C)
+constexpr int kMapBadScore = 1, kMapBadCoordinate = 2, kMapBadBox = 4, kMapBadLabel = 8;
+struct MapMatchArgs {
+  const float* det_boxes = nullptr;    // [M, 4]
+  const void* det_scores = nullptr;    // [M], f32 / f16 / bf16
+  DType score_dt = DType::f32;
+  const void* det_labels = nullptr;    // [M], i64 / i32
+  DType det_label_dt = DType::i64;
+  const float* gt_boxes = nullptr;     // [G, 4]
+  const void* gt_labels = nullptr;     // [G], i64 / i32
+  DType gt_label_dt = DType::i64;
+  const int64_t* offsets = nullptr;    // [2, B + 1] on the device: first detection / ground truth of an image
+  const double* thresholds = nullptr;  // [T]
+  int num_images = 0;
+  int num_thresholds = 0;
+  int num_classes = 0;
+  int max_detections = 0;
+  float* scores = nullptr;             // [M]: every image's detections in the matching order
+  int32_t* labels = nullptr;           // [M]: -1 for a dropped detection
+  int32_t* hits = nullptr;             // [M]: bit k, matched under threshold k
+  long long* gt_count = nullptr;       // [C]: += ground truths per class
+  int32_t* matched_gt = nullptr;       // [M, T] or null: index within the image of the matched ground truth, -1
+  int* err = nullptr;                  // or null: |= kMapBad* bits
+};
+int launch_map_match(const MapMatchArgs& a, hipStream_t stream);
+struct MapCurveArgs {
+  const int32_t* hits = nullptr;       // [N] in the global order (label, score descending, stored order)
+  const int64_t* class_offsets = nullptr;  // [C + 1]
+  const double* gt_count = nullptr;    // [C]
+  int num_classes = 0;
+  int num_thresholds = 0;
+  int index_50 = -1;                   // rows of the thresholds 0.5 and 0.75, -1 when absent
+  int index_75 = -1;
+  double* ap = nullptr;                // [T, C], NaN for a class without ground truth
+  double* rec = nullptr;               // [T, C]
+  float* scalars = nullptr;            // [4]: map, map_50, map_75, mar
+  float* map_per_class = nullptr;      // [C]
+  float* mar_per_class = nullptr;      // [C]
+};
+int launch_map_curve(const MapCurveArgs& a, hipStream_t stream);  // two launches
+}  // namespace tea

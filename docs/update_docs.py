@@ -35,6 +35,7 @@ PAGES: Dict[str, Tuple[str, str, List[str]]] = {
             "torcheval_amd.metrics.aggregation",
             "torcheval_amd.metrics.classification",
             "torcheval_amd.metrics.clustering",
+            "torcheval_amd.metrics.detection",
             "torcheval_amd.metrics.image",
             "torcheval_amd.metrics.ranking",
             "torcheval_amd.metrics.regression",
@@ -49,6 +50,7 @@ PAGES: Dict[str, Tuple[str, str, List[str]]] = {
             "torcheval_amd.metrics.functional.aggregation",
             "torcheval_amd.metrics.functional.classification",
             "torcheval_amd.metrics.functional.clustering",
+            "torcheval_amd.metrics.functional.detection",
             "torcheval_amd.metrics.functional.image",
             "torcheval_amd.metrics.functional.ranking",
             "torcheval_amd.metrics.functional.regression",

@@ -89,8 +89,13 @@ def _flags(kind: str) -> List[str]:
 # Extra flags of single translation units, by file name.  classification.hip: the K1 micro
 # update and fold kernels take plain pointer / integer parameters, which the dispatcher preloads
 # into SGPRs under this flag (kernels whose arguments are one struct by value are not affected).
+# detection_map.hip: K24's IoU is one rounded FP64 operation per step on every path, and under
+# -ffp-contract=fast the backend fuses across a `#pragma clang fp contract(off)` body once it is
+# inlined (it did: v_fma_f64 of area and intersection), so the unit is built without contraction
+# (the last -ffp-contract wins).
 FILE_FLAGS = {
     "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
+    "detection_map.hip": ["-ffp-contract=off"],
 }
 
 
