@@ -13,6 +13,11 @@
 //          kernels' plain parameters are preloaded into SGPRs (as torcheval_amd/ops/build.py
 //          compiles classification.hip); in the first compile the same kernels fetch them
 //          with scalar loads at the head of every wave
+//   head variants (preloaded compile, profiles/k1_oneshot_ab.json): what the instructions between
+//          a wave's entry point and its row loads cost.  The read floor with 64 / 128 / 256 bytes
+//          of s_nop in front of the loads; cls_micro_pend_kernel's head in front of the read
+//          body; the loop arm and the one-shot arm of the production launch, launched directly;
+//          each at 8 and at 4 waves per workgroup.  Five interleaved rounds, min / median / max.
 //
 // Two objects from this one file (the preload flag holds for a whole translation unit):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icsrc/include -c csrc/bench/k1_floor.hip -o k1_floor.o
@@ -75,7 +80,111 @@ void k1_floor_read_preload(const float* x, const int64_t* y, float* sink, hipStr
 int k1_floor_prod_preload(const ClsCountsArgs& a, hipStream_t s);
 int k1_floor_finish_preload(unsigned long long* pend, float* correct, const float* total, float* out, hipStream_t s);
 
+// the head-attribution variants (profiles/k1_oneshot_ab.json), all preloaded, all 8192 waves
+int k1_floor_head_variants();
+const char* k1_floor_head_name(int which);
+void k1_floor_head_launch(int which, const float* x, const int64_t* y, float* sink, unsigned long long* pend,
+                          float* total, hipStream_t s);
+
 #ifdef K1_FLOOR_PRELOAD_UNIT
+
+namespace {
+
+// the pure-read body with WPB waves per workgroup and PAD s_nop (4 bytes each) between the entry
+// point and the first load: 16 of them push the loads one 64-byte instruction line further away
+template <int WPB, int PAD>
+__global__ __launch_bounds__(WPB * 64) void read_pad_kernel(const float* __restrict__ x, const int64_t* __restrict__ y,
+                                                            float* __restrict__ sink) {
+#pragma unroll
+  for (int i = 0; i < PAD; ++i) asm volatile("s_nop 0");
+  const int lane = threadIdx.x & 63;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * WPB + (threadIdx.x >> 6);
+  const float* rp = x + row * C;
+  float m = -__builtin_huge_valf();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int col = u * FSTEP + lane * 4;
+    const float4 q = *reinterpret_cast<const float4*>(rp + (col < C ? col : 0));
+    m = fmaxf(m, fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w)));
+  }
+  const int64_t t = y[row];
+  if (m == 12345.678f && t == 7) sink[row] = m;
+}
+
+// cls_micro_pend_kernel's head (run-time n, c and row_stride, the 64-bit row clamp and multiply,
+// a column clamp per load) in front of the pure-read body
+template <int WPB>
+__global__ __launch_bounds__(WPB * 64) void prodhead_read_kernel(const char* __restrict__ input,
+                                                                 const int64_t* __restrict__ target,
+                                                                 float* __restrict__ sink, int64_t n,
+                                                                 int64_t row_stride, int32_t c) {
+  const int lane = lane_id();
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * WPB + wave_id();
+  const int64_t r0 = row0 < n ? row0 : n - 1;
+  const char* rp = input + r0 * row_stride * 4;
+  float f[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) load_row_vec<0, 4, false>(rp, u * FSTEP + lane * 4, c, f[u]);
+  const int64_t t = target[r0];
+  __builtin_amdgcn_sched_barrier(0);  // as in production, no use of a loaded value ahead of the last load
+  float m = fmaximum(f[0][0], f[0][1]);
+#pragma unroll
+  for (int e = 2; e < 16; ++e) m = fmaximum(m, f[e / 4][e % 4]);
+  if (m == 12345.678f && t == 7) sink[r0] = m;
+}
+
+constexpr int kHeadVariants = 11;
+const char* const kHeadNames[kHeadVariants] = {
+    "read floor, 8 waves per workgroup",
+    "read floor + 64 B of s_nop",
+    "read floor + 128 B of s_nop",
+    "read floor + 256 B of s_nop",
+    "production head + read body, 8 waves per workgroup",
+    "loop arm (cls_micro_pend_kernel), 8 waves per workgroup",
+    "one-shot arm (cls_micro_oneshot_kernel), 8 waves per workgroup",
+    "read floor, 4 waves per workgroup",
+    "production head + read body, 4 waves per workgroup",
+    "loop arm (cls_micro_pend_kernel), 4 waves per workgroup",
+    "one-shot arm (cls_micro_oneshot_kernel), 4 waves per workgroup",
+};
+
+}  // namespace
+
+int k1_floor_head_variants() { return kHeadVariants; }
+const char* k1_floor_head_name(int which) { return kHeadNames[which]; }
+void k1_floor_head_launch(int which, const float* x, const int64_t* y, float* sink, unsigned long long* pend,
+                          float* total, hipStream_t s) {
+  const char* in = reinterpret_cast<const char*>(x);
+  const dim3 g8(N / 8), b8(512), g4(N / 4), b4(256);
+  const int64_t n = N, stride = C;
+  const uint32_t n32 = N, row_bytes = C * 4;
+  const int32_t c = C;
+  switch (which) {
+    case 0: hipLaunchKernelGGL((read_pad_kernel<8, 0>), g8, b8, 0, s, x, y, sink); break;
+    case 1: hipLaunchKernelGGL((read_pad_kernel<8, 16>), g8, b8, 0, s, x, y, sink); break;
+    case 2: hipLaunchKernelGGL((read_pad_kernel<8, 32>), g8, b8, 0, s, x, y, sink); break;
+    case 3: hipLaunchKernelGGL((read_pad_kernel<8, 64>), g8, b8, 0, s, x, y, sink); break;
+    case 4: hipLaunchKernelGGL((prodhead_read_kernel<8>), g8, b8, 0, s, in, y, sink, n, stride, c); break;
+    case 5:
+      hipLaunchKernelGGL((cls_micro_pend_kernel<0, int64_t, 8, false>), g8, b8, 0, s, in, y, pend, total, n, stride, c,
+                         N);
+      break;
+    case 6:
+      hipLaunchKernelGGL((cls_micro_oneshot_kernel<0, int64_t, 8, C / FSTEP>), g8, b8, 0, s, in, y, pend, total, n32,
+                         row_bytes, c);
+      break;
+    case 7: hipLaunchKernelGGL((read_pad_kernel<4, 0>), g4, b4, 0, s, x, y, sink); break;
+    case 8: hipLaunchKernelGGL((prodhead_read_kernel<4>), g4, b4, 0, s, in, y, sink, n, stride, c); break;
+    case 9:
+      hipLaunchKernelGGL((cls_micro_pend_kernel<0, int64_t, 4, false>), g4, b4, 0, s, in, y, pend, total, n, stride, c,
+                         N);
+      break;
+    default:
+      hipLaunchKernelGGL((cls_micro_oneshot_kernel<0, int64_t, 4, C / FSTEP>), g4, b4, 0, s, in, y, pend, total, n32,
+                         row_bytes, c);
+      break;
+  }
+}
 
 void k1_floor_read_preload(const float* x, const int64_t* y, float* sink, hipStream_t s) {
   hipLaunchKernelGGL(read_floor_kernel, dim3(N / 4), dim3(256), 0, s, x, y, sink);
@@ -307,6 +416,14 @@ int main(int argc, char** argv) {
     best[11] = std::min(best[11], time_it(readpl, iters, e0, e1));
     best[12] = std::min(best[12], time_it(prodpl, iters, e0, e1));
   }
+  // the head-attribution variants: interleaved over 5 rounds, every round kept
+  constexpr int HR = 5;
+  const int nh = k1_floor_head_variants();
+  std::vector<std::vector<float>> head(nh);
+  for (int r = 0; r < HR; ++r)
+    for (int v = 0; v < nh; ++v)
+      head[v].push_back(time_it(
+          [&](int i) { k1_floor_head_launch(v, xs[i % POOL], ys[i % POOL], sink, pend, total, 0); }, iters, e0, e1));
   const double bytes = static_cast<double>(N) * C * 4 + N * 8;
   const char* names[NV] = {"prod (launch_cls_counts micro)", "read floor (same geometry)", "empty (2048 x 256)",
                            "read floor behind ClsCountsArgs", "read floor + one atomic", "read floor + DPP max + target compare",
@@ -316,6 +433,11 @@ int main(int argc, char** argv) {
   for (int v = 0; v < NV; ++v)
     printf("{\"variant\": \"%s\", \"pool\": %d, \"us_per_launch\": %.3f, \"TBps\": %.2f}\n", names[v], POOL, best[v],
            (v != 2 && (v < 9 || v > 10)) ? bytes / (best[v] * 1e-6) / 1e12 : 0.0);
+  for (int v = 0; v < nh; ++v) {
+    std::sort(head[v].begin(), head[v].end());
+    printf("{\"head_variant\": \"%s\", \"pool\": %d, \"us_min\": %.3f, \"us_median\": %.3f, \"us_max\": %.3f}\n",
+           k1_floor_head_name(v), POOL, head[v].front(), head[v][HR / 2], head[v].back());
+  }
   printf("{\"prod_over_floor\": %.4f}\n", best[0] / best[1]);
   printf("{\"prod_preloaded_over_prod\": %.4f, \"read_preloaded_over_read\": %.4f}\n", best[12] / best[0],
          best[11] / best[1]);

@@ -25,6 +25,7 @@
 //    (bit 0: target out of range, bit 1: predicted label out of range).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "tea_common.h"
 #include "tea_fold.h"
@@ -493,16 +494,15 @@ __global__ __launch_bounds__(kBlock) void cls_micro_kernel(ClsCountsArgs a) {
 // (gridDim.x is a hidden argument, which is not preloaded), so the kernel body holds no argument
 // load at all.  The row test needs no lane masks (profiles/k1_floor_r4*.txt,
 // profiles/k1_head_tail_ab.json).
-template <int KIND, typename TGT, bool UNAL>
-__device__ __forceinline__ bool micro_row(int C, const char* __restrict__ rp, int64_t t, int lane) {
-  constexpr int VEC = KIND == 0 ? 4 : 8;
+//
+// The row test on a lane's loaded values, shared by both arms of that launch: f[u][e] holds
+// nominal column u * STEP + lane * VEC + e.
+template <int KIND, int VEC>
+__device__ __forceinline__ bool micro_row_test(const float (&f)[kChunkLoads][VEC], int C,
+                                               const char* __restrict__ rp, int64_t t, int lane) {
   constexpr int NV = kChunkLoads * VEC;
   constexpr int STEP = kWave * VEC;
   typedef typename RowVals<NV>::type vec_t;
-  float f[kChunkLoads][VEC];
-#pragma unroll
-  for (int u = 0; u < kChunkLoads; ++u) load_row_vec<KIND, VEC, UNAL>(rp, u * STEP + lane * VEC, C, f[u]);
-  if constexpr (UNAL) unal_fix_tail<kChunkLoads>(f, 0, C, lane);
   vec_t v;
 #pragma unroll
   for (int u = 0; u < kChunkLoads; ++u)
@@ -528,6 +528,56 @@ __device__ __forceinline__ bool micro_row(int C, const char* __restrict__ rp, in
 #pragma unroll
     for (int e = 0; e < VEC; ++e) tie |= (v[u * VEC + e] == xt) & (u * STEP + lane * VEC + e < tu);  // no branches
   return __ballot(tie) == 0;
+}
+
+template <int KIND, typename TGT, bool UNAL>
+__device__ __forceinline__ bool micro_row(int C, const char* __restrict__ rp, int64_t t, int lane) {
+  constexpr int VEC = KIND == 0 ? 4 : 8;
+  constexpr int STEP = kWave * VEC;
+  float f[kChunkLoads][VEC];
+#pragma unroll
+  for (int u = 0; u < kChunkLoads; ++u) load_row_vec<KIND, VEC, UNAL>(rp, u * STEP + lane * VEC, C, f[u]);
+  if constexpr (UNAL) unal_fix_tail<kChunkLoads>(f, 0, C, lane);
+  return micro_row_test<KIND, VEC>(f, C, rp, t, lane);
+}
+
+// The one-shot arm of the north-star launch: every wave owns at most one row (n <= waves of the
+// grid), the rows are 16-B aligned and the last row's chunk ends below 2^31 bytes, so the head in
+// front of the row loads is 32-bit scalar work only: a scalar min clamps the row, one s_mul_i32
+// with the host's row size in bytes gives its offset, and the lane's one byte offset serves
+// every load.  FULL = wave-loads that lie wholly inside the row (C / STEP, uniform per launch):
+// they take immediate offsets and no clamp.  Only wave-load FULL can cross C and keeps the
+// clamp; the ones behind it lie wholly past C and read columns 0..VEC-1 (the clamp's value
+// there) from a zero offset.  No grid-stride loop, one copy of the row test; the epilogue is
+// cls_micro_pend_kernel's.  At the benchmark's shape the fourth load issues after 22 instructions
+// (116 bytes from the entry point) against 46, the kernel is 1596 bytes against 3052, and a
+// launch takes 5.76 us against 5.92 in the floor harness (profiles/k1_oneshot_ab.json).
+template <int KIND, typename TGT, int WPB, int FULL>
+__global__ __launch_bounds__(WPB * kWave) void cls_micro_oneshot_kernel(const char* __restrict__ input,
+                                                                        const TGT* __restrict__ target,
+                                                                        unsigned long long* __restrict__ pend,
+                                                                        float* __restrict__ total, uint32_t n,
+                                                                        uint32_t row_bytes, int32_t c) {
+  constexpr int VEC = KIND == 0 ? 4 : 8;
+  constexpr int STEP = kWave * VEC;
+  constexpr uint32_t kLoadBytes = kWave * 16;
+  const int lane = lane_id();
+  const uint32_t row0 = blockIdx.x * WPB + wave_id();
+  const uint32_t r0 = min(row0, n - 1);  // the launcher guarantees n >= 1
+  const char* rp = input + r0 * row_bytes;  // 32-bit product (launch_micro_oneshot checks the last row)
+  const uint32_t voff = static_cast<uint32_t>(lane) * 16u;
+  float f[kChunkLoads][VEC];
+#pragma unroll
+  for (int u = 0; u < kChunkLoads; ++u) {
+    uint32_t off = voff + u * kLoadBytes;
+    if (u == FULL) off = u * STEP + lane * VEC < c ? off : 0u;
+    if (u > FULL) off = 0u;
+    load_vec<KIND, VEC>(rp + off, 0, f[u]);
+  }
+  const bool c0 = micro_row_test<KIND, VEC>(f, c, rp, target[r0], lane);
+  if (lane == 0 && row0 < n && c0)
+    atomicAdd(pend + (row0 % kPendCells) * kPendStride, 1ull);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && total) atomicAdd(total, static_cast<float>(n));
 }
 
 template <int KIND, typename TGT, int WPB, bool UNAL>
@@ -700,6 +750,35 @@ __global__ __launch_bounds__(kBlock) void binary_counts_kernel(BinaryCountsArgs 
   if (threadIdx.x == 0 && blockIdx.x == 0 && a.total) atomicAdd(a.total, static_cast<float>(a.n));
 }
 
+// The one-shot arm of the pending-cell launch (aligned rows only; the caller holds that).  False,
+// and nothing launched, unless every wave of the grid gets at most one row and the byte offset of
+// the last row's chunk fits 32 bits; the caller then launches cls_micro_pend_kernel.
+template <int KIND, typename TGT, int WPB>
+bool launch_micro_oneshot(const ClsCountsArgs& a, int grid, hipStream_t s) {
+  constexpr int STEP = kWave * (KIND == 0 ? 4 : 8);
+  constexpr int64_t kChunkBytes = kChunkLoads * kWave * 16;
+  const int64_t row_bytes = a.row_stride * kind_bytes<KIND>;
+  if (a.n > static_cast<int64_t>(grid) * WPB || row_bytes < 0 ||
+      (a.n - 1) * row_bytes + kChunkBytes >= (int64_t{1} << 31))
+    return false;
+  const char* in = static_cast<const char*>(a.input);
+  const TGT* tg = static_cast<const TGT*>(a.target);
+  const uint32_t n = static_cast<uint32_t>(a.n), rb = static_cast<uint32_t>(row_bytes);
+  const int32_t c = static_cast<int32_t>(a.c);
+  auto go = [&](auto full) {
+    hipLaunchKernelGGL((cls_micro_oneshot_kernel<KIND, TGT, WPB, decltype(full)::value>), dim3(grid),
+                       dim3(WPB * kWave), 0, s, in, tg, a.pend, a.micro_total, n, rb, c);
+  };
+  switch (std::min(c / STEP, kChunkLoads)) {  // wave-loads wholly inside the row
+    case 0: go(std::integral_constant<int, 0>{}); break;
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 3: go(std::integral_constant<int, 3>{}); break;
+    default: go(std::integral_constant<int, 4>{}); break;
+  }
+  return true;
+}
+
 template <int KIND, int VEC, bool UNAL = false>
 void launch_wide(const ClsCountsArgs& a, int grid, hipStream_t s) {
   constexpr int kChunkCols = kWave * VEC * kChunkLoads;
@@ -719,13 +798,19 @@ void launch_wide(const ClsCountsArgs& a, int grid, hipStream_t s) {
     // 512-thread workgroups (8 waves, still one wave per row, 1024 blocks): the driver command
     // 144.9k vs 142.7k updates/s with 4-wave workgroups, interleaved on one box, and the floor
     // harness 6.23 vs 6.30 us per launch (profiles/k1_wpb_ab_r4.txt).  TORCHEVAL_AMD_K1_WPB=4
-    // selects the 256-thread form.
+    // selects the 256-thread form.  Measured again on the one-shot arm: 5.76 us with 8 waves
+    // against 5.80 with 4 (profiles/k1_oneshot_ab.json), so 8 stays.
     static const int wpb = [] {
       const char* e = std::getenv("TORCHEVAL_AMD_K1_WPB");
       return (e && std::atoi(e) == 4) ? 4 : 8;
     }();
     if (wpb == 8) {
       const int g8 = stream_grid(a.n, 8, a.max_blocks > 0 ? (a.max_blocks + 1) / 2 : 1024);
+      if constexpr (!UNAL) {
+        if (a.tg_dt == DType::i64 ? launch_micro_oneshot<KIND, int64_t, 8>(a, g8, s)
+                                  : launch_micro_oneshot<KIND, int32_t, 8>(a, g8, s))
+          return;
+      }
       if (a.tg_dt == DType::i64)
         hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, in,
                            static_cast<const int64_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c, g8 * 8);
@@ -733,6 +818,11 @@ void launch_wide(const ClsCountsArgs& a, int grid, hipStream_t s) {
         hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int32_t, 8, UNAL>), dim3(g8), dim3(8 * kWave), 0, s, in,
                            static_cast<const int32_t*>(a.target), a.pend, a.micro_total, a.n, a.row_stride, c, g8 * 8);
       return;
+    }
+    if constexpr (!UNAL) {
+      if (a.tg_dt == DType::i64 ? launch_micro_oneshot<KIND, int64_t, kWavesPerBlock>(a, grid, s)
+                                : launch_micro_oneshot<KIND, int32_t, kWavesPerBlock>(a, grid, s))
+        return;
     }
     if (a.tg_dt == DType::i64)
       hipLaunchKernelGGL((cls_micro_pend_kernel<KIND, int64_t, kWavesPerBlock, UNAL>), dim3(grid), dim3(kBlock), 0, s, in,
