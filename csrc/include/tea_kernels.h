@@ -1123,3 +1123,76 @@ struct MapCurveArgs {
 };
 int launch_map_curve(const MapCurveArgs& a, hipStream_t stream);  // two launches
 }  // namespace tea
+
+namespace tea {
+// K25: pair-counting and information clustering indices of two labelings (csrc/kernels/contingency.hip;
+// docs/parity.md, "Not in the reference").  All of them are functions of the rectangular int64
+// contingency table n[i, j] = #{s : true[s] = i, pred[s] = j}.  contingency_count_kernel adds one
+// batch of label pairs to it: the table is cut into slices of S consecutive cells held in LDS as u32,
+// block (slice, group) walks its group's samples and counts the cells of its slice, and flushes the
+// non-zero cells with 64-bit integer atomics.  Integer sums only: bit-identical from run to run.
+constexpr int kCtgSliceSmall = 4096;    // cells of a small slice: 16 KiB of LDS, eight blocks of 256 threads per CU
+constexpr int kCtgSliceLarge = 32768;   // cells of a large slice: 128 KiB of a CU's 160 KiB, one block of 1024 threads
+constexpr int kCtgBlockSmall = 256;
+constexpr int kCtgBlockLarge = 1024;
+constexpr int kCtgUnit = 4;             // label pairs a thread takes per step (16-byte loads)
+constexpr int kCtgMaxBlocks = 1024;     // slices * groups of the count launch
+constexpr int kCtgMaxCells = 1 << 22;   // R * C of the native path
+constexpr int kCtgStatsBlocks = 1024;   // largest grid of the cell pass; its FP64 partials
+constexpr int kCtgMarginBlocks = 256;   // largest grid of the marginal pass
+constexpr int kCtgEmiBlocks = 2048;     // largest grid of the EMI launch
+constexpr int kCtgEmiMaxParts = 64;     // a pair's n-range is cut into at most this many wave-items
+constexpr int kCtgInts = 6;             // pairs of cells, of rows, of columns; N; non-empty rows, columns
+constexpr int kCtgValues = 21;          // length of the values vector (indices: ops/contingency.py)
+constexpr int kCtgBadLabel = 1;         // bit of the flag: a label outside its range
+struct ContingencyCountArgs {
+  const void* labels_true = nullptr;   // [n], i64 / i32
+  const void* labels_pred = nullptr;   // [n], i64 / i32
+  DType true_dt = DType::i64;
+  DType pred_dt = DType::i64;
+  int64_t n = 0;                       // < 2^31
+  int64_t r = 0;                       // rows: labels_true in [0, r)
+  int64_t c = 0;                       // columns: labels_pred in [0, c)
+  int slice = 0;                       // kCtgSliceSmall or kCtgSliceLarge
+  int groups = 0;                      // sample groups; ceil(r c / slice) * groups <= kCtgMaxBlocks
+  long long* table = nullptr;          // [r, c] += counts
+  int* err = nullptr;                  // or null: |= kCtgBadLabel
+};
+int launch_contingency_count(const ContingencyCountArgs& a, hipStream_t stream);
+// Blocks of the three statistics grids for an [r, c] table (lengths of the partial vectors)
+int contingency_stats_blocks(int64_t r, int64_t c);
+int contingency_margin_blocks(int64_t r, int64_t c);
+int contingency_emi_blocks(int64_t r, int64_t c);
+int contingency_emi_parts(int64_t r, int64_t c);
+struct ContingencyStatsArgs {
+  const long long* table = nullptr;    // [r, c], every cell >= 0 and the total < 2^32
+  int64_t r = 0;
+  int64_t c = 0;
+  long long* marginals = nullptr;      // [r + c], zero on entry: row sums, then column sums
+  unsigned long long* ints = nullptr;  // [kCtgInts], zero on entry
+  double* cell_partials = nullptr;     // [contingency_stats_blocks]: sums of n log n over the cells
+  double* margin_partials = nullptr;   // [2, contingency_margin_blocks]: sums of a log a, of b log b
+  double* margin_logs = nullptr;       // [2, r + c]: log x, then lgamma(x + 1) + lgamma(N - x + 1) (EMI's tables)
+};
+int launch_contingency_stats(const ContingencyStatsArgs& a, hipStream_t stream);  // two launches
+struct ContingencyEmiArgs {
+  const long long* marginals = nullptr;         // of launch_contingency_stats
+  const unsigned long long* ints = nullptr;
+  const double* margin_logs = nullptr;
+  int64_t r = 0;
+  int64_t c = 0;
+  double* partials = nullptr;                   // [2, contingency_emi_blocks]: sums of the terms, of their magnitudes
+};
+int launch_contingency_emi(const ContingencyEmiArgs& a, hipStream_t stream);
+struct ContingencyValuesArgs {
+  const unsigned long long* ints = nullptr;
+  const double* cell_partials = nullptr;
+  const double* margin_partials = nullptr;
+  const double* emi_partials = nullptr;         // or null: EMI and AMI come out NaN
+  int stats_blocks = 0;
+  int margin_blocks = 0;
+  int emi_blocks = 0;
+  double* values = nullptr;                     // [kCtgValues]
+};
+int launch_contingency_values(const ContingencyValuesArgs& a, hipStream_t stream);
+}  // namespace tea

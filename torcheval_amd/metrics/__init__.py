@@ -9,6 +9,17 @@ from torcheval_amd.metrics.classification import __all__ as _cls_all
 from torcheval_amd.metrics.classification import MulticlassCalibrationError  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.classification import DiceScore, MeanIoU  # likewise
 from torcheval_amd.metrics.clustering import SilhouetteScore  # likewise
+from torcheval_amd.metrics.clustering import (  # likewise (K25)
+    AdjustedMutualInfoScore,
+    AdjustedRandScore,
+    CompletenessScore,
+    FowlkesMallowsScore,
+    HomogeneityScore,
+    MutualInfoScore,
+    NormalizedMutualInfoScore,
+    RandScore,
+    VMeasureScore,
+)
 from torcheval_amd.metrics.detection import MeanAveragePrecision  # likewise
 from torcheval_amd.metrics.image import PeakSignalNoiseRatio
 from torcheval_amd.metrics.image import StructuralSimilarity  # not a reference name: kept out of __all__

@@ -1,8 +1,31 @@
 """Clustering metrics, class API (none of them a reference name)."""
 
+from torcheval_amd.metrics.clustering.contingency import (
+    AdjustedMutualInfoScore,
+    AdjustedRandScore,
+    CompletenessScore,
+    FowlkesMallowsScore,
+    HomogeneityScore,
+    MutualInfoScore,
+    NormalizedMutualInfoScore,
+    RandScore,
+    VMeasureScore,
+)
 from torcheval_amd.metrics.clustering.silhouette import SilhouetteScore
 
 __all__ = [
     "SilhouetteScore",
+]
+# documented, outside the pinned __all__ (K25: the indices of a contingency table)
+__doc_extras__ = [
+    "RandScore",
+    "AdjustedRandScore",
+    "MutualInfoScore",
+    "NormalizedMutualInfoScore",
+    "AdjustedMutualInfoScore",
+    "HomogeneityScore",
+    "CompletenessScore",
+    "VMeasureScore",
+    "FowlkesMallowsScore",
 ]
 __doc_name__ = "Clustering Metrics"

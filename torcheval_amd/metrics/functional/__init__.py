@@ -6,6 +6,18 @@ from torcheval_amd.metrics.functional.classification import __all__ as _cls_all
 from torcheval_amd.metrics.functional.classification import multiclass_calibration_error  # not in __all__
 from torcheval_amd.metrics.functional.classification import dice_score, mean_iou  # likewise
 from torcheval_amd.metrics.functional.clustering import silhouette_samples, silhouette_score  # likewise
+from torcheval_amd.metrics.functional.clustering import (  # likewise (K25)
+    adjusted_mutual_info_score,
+    adjusted_rand_score,
+    completeness_score,
+    contingency_matrix,
+    fowlkes_mallows_score,
+    homogeneity_score,
+    mutual_info_score,
+    normalized_mutual_info_score,
+    rand_score,
+    v_measure_score,
+)
 from torcheval_amd.metrics.functional.detection import mean_average_precision  # likewise
 from torcheval_amd.metrics.functional.image import peak_signal_noise_ratio
 from torcheval_amd.metrics.functional.image import structural_similarity  # not a reference name: kept out of __all__
