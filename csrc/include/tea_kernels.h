@@ -1196,3 +1196,44 @@ struct ContingencyValuesArgs {
 };
 int launch_contingency_values(const ContingencyValuesArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K26: multi-scale SSIM of contiguous [n, c, h, w] image pairs (csrc/kernels/msssim.hip).  Level 0 is
+// the input pair and level j + 1 the 2 x 2 average of level j (floor).  Levels whose plane does not
+// fit one K12 halo run one launch each on K12's tiles and write the pooled pair of the next level into
+// the workspace; from the first level that fits (`tail`) one launch runs all remaining levels out of
+// LDS; the finish launch turns the per-(plane, level, tile) FP64 partials into the values.
+constexpr int kMsssimMaxLevels = 8;
+struct MsssimPlan {
+  int levels = 0;
+  int tail = 0;                          // first level of the tail launch; == levels: no tail launch
+  int h[kMsssimMaxLevels] = {};          // plane sizes per level
+  int w[kMsssimMaxLevels] = {};
+  int64_t per[kMsssimMaxLevels] = {};    // partials per plane: the level's tiles, 1 in the tail
+  int64_t part_off[kMsssimMaxLevels] = {};  // partials of all earlier levels, per plane
+  int64_t ws_off[kMsssimMaxLevels] = {};    // (x, y) pairs of the workspace levels before j, per plane (j >= 1)
+  int64_t partials = 0;                  // per plane
+  int64_t ws_pairs = 0;                  // per plane: levels 1 .. min(tail, levels - 1)
+};
+bool msssim_geometry_ok(int64_t planes, int64_t h, int64_t w, int64_t ks, int64_t levels);
+MsssimPlan msssim_plan(int64_t h, int64_t w, int64_t ks, int64_t levels);  // of an ok geometry
+struct MsssimArgs {
+  const void* x = nullptr;
+  const void* y = nullptr;
+  DType dt = DType::f32;  // f32 / f16 / bf16 / u8, both inputs
+  int64_t n = 0, c = 0;
+  int h = 0, w = 0;
+  int ks = 11;                        // odd, 3..kSsimMaxKs
+  float taps[kSsimMaxKs] = {};        // the 1-D window, normalised on the host in FP64
+  float c1 = 0.f, c2 = 0.f;
+  int levels = 0;                     // 1..kMsssimMaxLevels
+  double betas[kMsssimMaxLevels] = {};
+  float* workspace = nullptr;         // [n * c * plan.ws_pairs * 2] scratch (may be null when that is 0)
+  double* partial = nullptr;          // [n * c * plan.partials] scratch
+  float* out = nullptr;               // [n] values, or [1] mean when ``mean``; may be null
+  int mean = 0;
+  double* value_sum = nullptr;        // class states (both or neither): += sum of the n values, += n
+  double* num_images = nullptr;
+};
+int launch_msssim(const MsssimArgs& a, hipStream_t stream);
+}  // namespace tea

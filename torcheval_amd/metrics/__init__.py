@@ -24,6 +24,7 @@ from torcheval_amd.metrics.detection import MeanAveragePrecision  # likewise
 from torcheval_amd.metrics.image import PeakSignalNoiseRatio
 from torcheval_amd.metrics.image import StructuralSimilarity  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.image import KernelInceptionDistance  # likewise
+from torcheval_amd.metrics.image import MultiScaleStructuralSimilarity  # likewise
 from torcheval_amd.metrics.image import InceptionScore  # likewise
 from torcheval_amd.metrics.image import DensityCoverage, ImprovedPrecisionRecall  # likewise
 from torcheval_amd.metrics.metric import Metric

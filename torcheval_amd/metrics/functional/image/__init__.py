@@ -2,6 +2,7 @@
 
 from torcheval_amd.metrics.functional.image.inception_score import inception_score
 from torcheval_amd.metrics.functional.image.kid import kernel_inception_distance
+from torcheval_amd.metrics.functional.image.msssim import multiscale_structural_similarity
 from torcheval_amd.metrics.functional.image.prdc import density_coverage, improved_precision_recall
 from torcheval_amd.metrics.functional.image.psnr import (
     peak_signal_noise_ratio,
@@ -16,6 +17,7 @@ __all__ = [
     "density_coverage",
     "improved_precision_recall",
     "kernel_inception_distance",
+    "multiscale_structural_similarity",
     "peak_signal_noise_ratio",
     "structural_similarity",
 ]

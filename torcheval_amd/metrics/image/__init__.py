@@ -6,6 +6,7 @@ resolves on first access), so importing the metrics package never needs a vision
 
 from torcheval_amd.metrics.image.inception_score import InceptionScore
 from torcheval_amd.metrics.image.kid import KernelInceptionDistance
+from torcheval_amd.metrics.image.msssim import MultiScaleStructuralSimilarity
 from torcheval_amd.metrics.image.prdc import DensityCoverage, ImprovedPrecisionRecall
 from torcheval_amd.metrics.image.psnr import PeakSignalNoiseRatio
 from torcheval_amd.metrics.image.ssim import StructuralSimilarity
@@ -15,6 +16,7 @@ __all__ = [
     "FrechetInceptionDistance",
     "ImprovedPrecisionRecall",
     "KernelInceptionDistance",
+    "MultiScaleStructuralSimilarity",
     "PeakSignalNoiseRatio",
     "StructuralSimilarity",
 ]

@@ -93,9 +93,18 @@ def _flags(kind: str) -> List[str]:
 # -ffp-contract=fast the backend fuses across a `#pragma clang fp contract(off)` body once it is
 # inlined (it did: v_fma_f64 of area and intersection), so the unit is built without contraction
 # (the last -ffp-contract wins).
+# msssim.hip: K26's (x, y) pair arithmetic is written on two-float vectors and is built to plain
+# FP32 instructions (the packed FP32 target feature off).  With the packed forms the register
+# allocator needs aligned VGPR pairs for the 3 x 16 accumulators of the band walk, and
+# `msssim_tail_kernel<*, 11>`, whose unrolled walk sits inside the run-time loop over the levels,
+# comes out at 256 VGPRs with 708-912 B/lane of scratch and occupancy 1; the `ks = 11` level kernels
+# rise from 96-104 to 103-105 VGPRs (occupancy 5 -> 4).  With plain FP32 the tail takes 142 VGPRs and
+# nothing spills.  Every figure and timing quoted for K26 (README, profiles/msssim_r41.json) and its
+# "no scratch" property hold for this flag only; the packed build was never run.
 FILE_FLAGS = {
     "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
     "detection_map.hip": ["-ffp-contract=off"],
+    "msssim.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
