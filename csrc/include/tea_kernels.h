@@ -1237,3 +1237,42 @@ struct MsssimArgs {
 };
 int launch_msssim(const MsssimArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K27: Hausdorff and average surface distance of integer label-map pairs [n, h, w]
+// (csrc/kernels/surface_distance.hip; docs/parity.md, "Not in the reference").  A plane is (image,
+// class, side), side 0 the prediction and 1 the target: plane = (image * classes + k) * 2 + side, and
+// column k is the class k + class_base.  The row launch writes, per plane, the distance along the row
+// to the nearest surface pixel (u16, kSurfNone: none in this row) and counts the surface pixels; the
+// search launch walks the other side's column at every surface pixel and writes its squared distance
+// (u32, kSurfNoPixel elsewhere); the finish launch reduces each plane and the combine launch forms the
+// values.  Unit spacing: every squared distance is an integer below 2^23, exact until the square root.
+constexpr int kSurfMaxSide = 2048;     // h, w <= this: a row distance fits 16 bits, a squared distance 23
+constexpr int kSurfMaxClasses = 64;    // the combine launch gives a class one lane of a wave
+constexpr uint16_t kSurfNone = 0xFFFF;
+constexpr uint32_t kSurfNoPixel = 0xFFFFFFFFu;
+struct SurfaceDistanceArgs {
+  const void* input = nullptr;   // [n, h, w] u8 / i8 / i16 / i32 / i64, contiguous
+  const void* target = nullptr;  // likewise
+  DType in_dt = DType::i64, tg_dt = DType::i64;
+  int64_t n = 0;
+  int h = 0, w = 0;              // 1 .. kSurfMaxSide
+  int classes = 0;               // columns of the result, 1 .. kSurfMaxClasses
+  int class_base = 0;            // 0, or 1 without the background class
+  int mode = 0;                  // 0: Hausdorff, 1: average surface distance
+  double quantile = -1.0;        // Hausdorff: percentile / 100, or < 0 for the maximum
+  int both = 1;                  // 1: both directions (undirected / symmetric), 0: input -> target only
+  uint16_t* g = nullptr;         // [planes, h, w] scratch
+  uint32_t* d2 = nullptr;        // [planes, h, w] scratch
+  uint32_t* counts = nullptr;    // [planes] scratch: surface pixels of the plane
+  double* partial = nullptr;     // [planes, 2] scratch: the direction's Hausdorff value and distance sum
+  float* out = nullptr;          // [n, classes]; may be null
+  // class states, all or none: [classes] += the finite values, their number, the number of +inf
+  double* value_sum = nullptr;
+  double* num_finite = nullptr;
+  double* num_inf = nullptr;
+};
+inline int64_t surface_distance_planes(int64_t n, int64_t classes) { return n * classes * 2; }
+bool surface_distance_geometry_ok(int64_t n, int64_t h, int64_t w, int64_t classes);
+int launch_surface_distance(const SurfaceDistanceArgs& a, hipStream_t stream);
+}  // namespace tea

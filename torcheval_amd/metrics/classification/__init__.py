@@ -37,6 +37,10 @@ from torcheval_amd.metrics.classification.recall_at_fixed_precision import (
     BinaryRecallAtFixedPrecision,
     MultilabelRecallAtFixedPrecision,
 )
+from torcheval_amd.metrics.classification.surface_distance import (  # noqa: F401  (not reference names either)
+    AverageSurfaceDistance,
+    HausdorffDistance,
+)
 
 __all__ = [
     "BinaryAccuracy",
@@ -72,4 +76,4 @@ __all__ = [
     "TopKMultilabelAccuracy",
 ]
 __doc_name__ = "Classification Metrics"
-__doc_extras__ = ["DiceScore", "MeanIoU"]  # documented, not reference names
+__doc_extras__ = ["AverageSurfaceDistance", "DiceScore", "HausdorffDistance", "MeanIoU"]  # documented, not reference names

@@ -54,6 +54,10 @@ from torcheval_amd.metrics.functional.classification.recall_at_fixed_precision i
     binary_recall_at_fixed_precision,
     multilabel_recall_at_fixed_precision,
 )
+from torcheval_amd.metrics.functional.classification.surface_distance import (  # noqa: F401  (likewise)
+    average_surface_distance,
+    hausdorff_distance,
+)
 
 __all__ = [
     "binary_accuracy",
@@ -89,4 +93,4 @@ __all__ = [
     "topk_multilabel_accuracy",
 ]
 __doc_name__ = "Classification Metrics"
-__doc_extras__ = ["dice_score", "mean_iou"]  # documented, not reference names
+__doc_extras__ = ["average_surface_distance", "dice_score", "hausdorff_distance", "mean_iou"]  # documented, not reference names

@@ -101,10 +101,13 @@ def _flags(kind: str) -> List[str]:
 # rise from 96-104 to 103-105 VGPRs (occupancy 5 -> 4).  With plain FP32 the tail takes 142 VGPRs and
 # nothing spills.  Every figure and timing quoted for K26 (README, profiles/msssim_r41.json) and its
 # "no scratch" property hold for this flag only; the packed build was never run.
+# surface_distance.hip: K27 is integer arithmetic up to one FP64 square root per surface pixel and has
+# nothing to pack; it is built like msssim.hip so that no packed FP32 form can appear in it.
 FILE_FLAGS = {
     "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
     "detection_map.hip": ["-ffp-contract=off"],
     "msssim.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "surface_distance.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
