@@ -1276,3 +1276,46 @@ inline int64_t surface_distance_planes(int64_t n, int64_t classes) { return n * 
 bool surface_distance_geometry_ok(int64_t n, int64_t h, int64_t w, int64_t classes);
 int launch_surface_distance(const SurfaceDistanceArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K28: panoptic quality of (category, instance) map pairs [n, p, 2] (csrc/kernels/panoptic.hip;
+// docs/parity.md, "Not in the reference").  The pairs launch reads both maps once: a block owns a span
+// of kPanSpan pixels of one image at a time, interns the span's canonical segments and (predicted,
+// target) pairs in LDS open-addressing tables and emits them as (pkey, tkey, count) into the span's
+// region of the workspace.  The match launch, one workgroup per image, merges the image's regions into
+// image-level tables and applies the matching rules; the finish launch adds the per-image partials in
+// image order into the four float64 class states.  A segment key is class << 32 | instance with the
+// class an index into the sorted category table; kPanVoidKey is the void segment.
+constexpr int kPanSpan = 1024;         // pixels per work item of the pairs launch (see panoptic.hip)
+constexpr int kPanMaxBlocks = 1024;    // cap of the persistent pairs grid
+constexpr int kPanMaxClasses = 1024;   // the category table and the class counters live in LDS
+constexpr int kPanMaxSegments = 1024;  // distinct segments per image and side, void included
+constexpr int kPanMaxPairs = 4096;     // distinct co-occurring pairs per image
+constexpr int kPanFlagUnknown = 1;     // flag bits: an unknown `input` category without the allow switch,
+constexpr int kPanFlagCapacity = 2;    // an image above kPanMaxSegments / kPanMaxPairs (it contributes nothing),
+constexpr int kPanFlagInstance = 4;    // a thing instance id outside [0, 2^32)
+struct PanopticArgs {
+  const void* input = nullptr;    // [n, p, 2] (category, instance), contiguous
+  const void* target = nullptr;   // likewise
+  int wide = 1;                   // 1: both maps int64, 0: both int32
+  int64_t n = 0, p = 0;           // images, pixels per image (p < 2^31)
+  const int64_t* table = nullptr; // [2, k]: the category ids ascending, then 1 for a thing class / 0 for stuff
+  int k = 0;                      // 1 .. kPanMaxClasses
+  int allow_unknown = 0;
+  unsigned long long* ws_keys = nullptr;  // [spans, 2, kPanSpan] scratch: pkey, tkey of a span's pairs
+  uint32_t* ws_counts = nullptr;          // [spans, kPanSpan] scratch: their pixel counts
+  uint32_t* ws_heads = nullptr;           // [spans] scratch: pairs of the span
+  unsigned long long* part_iou = nullptr; // [n, k] scratch: per image the sum of round(iou * 2^52)
+  uint32_t* part_counts = nullptr;        // [n, 3, k] scratch: tp, fp, fn
+  int* flag = nullptr;            // kPanFlag* bits, atomicOr
+  double* dst[4] = {nullptr, nullptr, nullptr, nullptr};  // [k] iou_sum, tp, fp, fn
+  int accumulate = 0;             // 1: dst += the batch, 0: dst = the batch
+  float* out = nullptr;           // null, or (PQ, SQ, RQ): [3] means, or [k, 3] when per_class
+  int per_class = 0;
+};
+inline int64_t panoptic_spans(int64_t n, int64_t p) { return n * ((p + kPanSpan - 1) / kPanSpan); }
+int launch_panoptic(const PanopticArgs& a, hipStream_t stream);
+// compute(): out <- (PQ, SQ, RQ) of the four [k] states, one single-wave launch
+int launch_panoptic_value(const double* iou_sum, const double* tp, const double* fp, const double* fn, int64_t k,
+                          int per_class, float* out, hipStream_t stream);
+}  // namespace tea

@@ -9,6 +9,7 @@ from torcheval_amd.metrics.classification import __all__ as _cls_all
 from torcheval_amd.metrics.classification import MulticlassCalibrationError  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.classification import DiceScore, MeanIoU  # likewise
 from torcheval_amd.metrics.classification import AverageSurfaceDistance, HausdorffDistance  # likewise
+from torcheval_amd.metrics.classification import PanopticQuality  # likewise
 from torcheval_amd.metrics.clustering import SilhouetteScore  # likewise
 from torcheval_amd.metrics.clustering import (  # likewise (K25)
     AdjustedMutualInfoScore,

@@ -26,6 +26,7 @@ from torcheval_amd.metrics.classification.confusion_matrix import (
 )
 from torcheval_amd.metrics.classification.f1_score import BinaryF1Score, MulticlassF1Score
 from torcheval_amd.metrics.classification.mean_iou import DiceScore, MeanIoU  # noqa: F401  (not reference names either)
+from torcheval_amd.metrics.classification.panoptic_quality import PanopticQuality  # noqa: F401  (not a reference name either)
 from torcheval_amd.metrics.classification.precision import BinaryPrecision, MulticlassPrecision
 from torcheval_amd.metrics.classification.precision_recall_curve import (
     BinaryPrecisionRecallCurve,
@@ -76,4 +77,4 @@ __all__ = [
     "TopKMultilabelAccuracy",
 ]
 __doc_name__ = "Classification Metrics"
-__doc_extras__ = ["AverageSurfaceDistance", "DiceScore", "HausdorffDistance", "MeanIoU"]  # documented, not reference names
+__doc_extras__ = ["AverageSurfaceDistance", "DiceScore", "HausdorffDistance", "MeanIoU", "PanopticQuality"]  # documented, not reference names

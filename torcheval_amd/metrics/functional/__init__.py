@@ -6,6 +6,7 @@ from torcheval_amd.metrics.functional.classification import __all__ as _cls_all
 from torcheval_amd.metrics.functional.classification import multiclass_calibration_error  # not in __all__
 from torcheval_amd.metrics.functional.classification import dice_score, mean_iou  # likewise
 from torcheval_amd.metrics.functional.classification import average_surface_distance, hausdorff_distance  # likewise
+from torcheval_amd.metrics.functional.classification import panoptic_quality  # likewise
 from torcheval_amd.metrics.functional.clustering import silhouette_samples, silhouette_score  # likewise
 from torcheval_amd.metrics.functional.clustering import (  # likewise (K25)
     adjusted_mutual_info_score,

@@ -40,6 +40,7 @@ from torcheval_amd.metrics.functional.classification.f1_score import (
     multiclass_f1_score,
 )
 from torcheval_amd.metrics.functional.classification.mean_iou import dice_score, mean_iou  # noqa: F401  (likewise)
+from torcheval_amd.metrics.functional.classification.panoptic_quality import panoptic_quality  # noqa: F401  (likewise)
 from torcheval_amd.metrics.functional.classification.precision import (
     binary_precision,
     multiclass_precision,
@@ -93,4 +94,4 @@ __all__ = [
     "topk_multilabel_accuracy",
 ]
 __doc_name__ = "Classification Metrics"
-__doc_extras__ = ["average_surface_distance", "dice_score", "hausdorff_distance", "mean_iou"]  # documented, not reference names
+__doc_extras__ = ["average_surface_distance", "dice_score", "hausdorff_distance", "mean_iou", "panoptic_quality"]  # documented, not reference names

@@ -103,11 +103,13 @@ def _flags(kind: str) -> List[str]:
 # "no scratch" property hold for this flag only; the packed build was never run.
 # surface_distance.hip: K27 is integer arithmetic up to one FP64 square root per surface pixel and has
 # nothing to pack; it is built like msssim.hip so that no packed FP32 form can appear in it.
+# panoptic.hip: K28 likewise (integer tables; FP64 in one division per match and in the values).
 FILE_FLAGS = {
     "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
     "detection_map.hip": ["-ffp-contract=off"],
     "msssim.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "surface_distance.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "panoptic.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
