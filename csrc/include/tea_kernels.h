@@ -1319,3 +1319,35 @@ int launch_panoptic(const PanopticArgs& a, hipStream_t stream);
 int launch_panoptic_value(const double* iou_sum, const double* tp, const double* fp, const double* fn, int64_t k,
                           int per_class, float* out, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K29: unit-cost Levenshtein distance of padded token-id rows (csrc/kernels/edit_distance.hip;
+// docs/parity.md, "Not in the reference").  Row b of a side is its first lengths[b] tokens (clamped to
+// [0, width]; the whole row without a length tensor) with every token equal to `ignore_index` removed.
+// A systolic wave walks the table in strips of 64 columns; the strip's left edge column lives in LDS as
+// 16-bit entries, which caps both widths at kEditMaxLen.
+constexpr int kEditMaxLen = 4096;
+constexpr int kEditArmWave = 0;    // one wave per pair, kEditPairsPerWg pairs per workgroup
+constexpr int kEditArmBlock = 1;   // one workgroup of kEditBlockWaves waves per pair
+constexpr int kEditPairsPerWg = 4;
+constexpr int kEditBlockWaves = 8;
+struct EditDistanceArgs {
+  const void* input = nullptr;    // [b, li] tokens, contiguous
+  const void* target = nullptr;   // [b, lt]
+  int wide = 0;                   // 1: both int64, 0: both int32
+  int64_t b = 0, li = 0, lt = 0;  // pairs and the two widths (0 .. kEditMaxLen)
+  const int64_t* input_lengths = nullptr;   // [b] or null: the width
+  const int64_t* target_lengths = nullptr;  // likewise
+  int has_ignore = 0;             // 1: the prep launch removes `ignore_index` into the workspace
+  int64_t ignore_index = 0;
+  void* ws_tokens = nullptr;      // has_ignore: b * (li + lt) tokens of the inputs' width
+  int64_t* ws_lengths = nullptr;  // has_ignore: [2, b] kept lengths
+  int arm = kEditArmWave;
+  int64_t* out = nullptr;         // [b] distances
+  // null (all four), or the 0-d totals: errors, input_total, target_total, max_total
+  double* totals[4] = {nullptr, nullptr, nullptr, nullptr};
+  int accumulate = 0;             // 1: totals += the batch, 0: totals = the batch
+};
+bool edit_distance_geometry_ok(int64_t b, int64_t li, int64_t lt);
+int launch_edit_distance(const EditDistanceArgs& a, hipStream_t stream);
+}  // namespace tea

@@ -36,6 +36,10 @@ from torcheval_amd.metrics.functional.text.perplexity import (
     _perplexity_label_check,
     _perplexity_input_check,
 )
+from torcheval_amd.metrics.functional.text.token_edit_distance import (  # noqa: F401  (not reference names: kept out of __all__)
+    token_edit_distance,
+    token_error_rate,
+)
 
 __all__ = [
     "bleu_score",
@@ -45,3 +49,4 @@ __all__ = [
     "word_information_preserved",
 ]
 __doc_name__ = "Text Metrics"
+__doc_extras__ = ["token_edit_distance", "token_error_rate"]  # documented, not reference names
