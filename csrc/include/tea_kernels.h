@@ -1351,3 +1351,38 @@ struct EditDistanceArgs {
 bool edit_distance_geometry_ok(int64_t b, int64_t li, int64_t lt);
 int launch_edit_distance(const EditDistanceArgs& a, hipStream_t stream);
 }  // namespace tea
+
+namespace tea {
+// K30: length of the longest common subsequence of padded token-id rows and the ROUGE-L sums over a batch
+// (csrc/kernels/lcs.hip; docs/parity.md, "Not in the reference").  Rows, lengths and `ignore_index` as K29.
+// The narrower side (by padded width; `input` on a tie) is stationary in `chunks` registers of 64 columns.
+constexpr int kLcsMaxLen = 4096;
+constexpr int kLcsMaxChunks = kLcsMaxLen / 64;
+constexpr int kLcsPairsPerWg = 4;
+struct LcsArgs {
+  const void* input = nullptr;    // [b, li] tokens, contiguous
+  const void* target = nullptr;   // [b, lt]
+  int wide = 0;                   // 1: both int64, 0: both int32
+  int64_t b = 0, li = 0, lt = 0;  // pairs and the two widths (0 .. kLcsMaxLen)
+  const int64_t* input_lengths = nullptr;   // [b] or null: the width
+  const int64_t* target_lengths = nullptr;  // likewise
+  int has_ignore = 0;             // 1: the prep launch removes `ignore_index` into the workspace
+  int64_t ignore_index = 0;
+  void* ws_tokens = nullptr;      // has_ignore: b * (li + lt) tokens of the inputs' width
+  int64_t* ws_lengths = nullptr;  // has_ignore: [2, b] kept lengths
+  int chunks = 1;                 // the kernel instance: a power of two in lcs_chunks(li, lt) .. kLcsMaxChunks
+  int64_t* out = nullptr;         // [b] LCS lengths
+  // null (all four), or the 0-d totals: the sums of precision, recall and F-measure, and the pairs
+  double* totals[4] = {nullptr, nullptr, nullptr, nullptr};
+  int accumulate = 0;             // 1: totals += the batch, 0: totals = the batch
+};
+// the smallest instance that holds the stationary side: pow2ceil(ceil(min(li, lt) / 64)), at least 1
+inline int lcs_chunks(int64_t li, int64_t lt) {
+  const int64_t need = ((li < lt ? li : lt) + 63) / 64;
+  int c = 1;
+  while (c < need) c *= 2;
+  return c;
+}
+bool lcs_geometry_ok(int64_t b, int64_t li, int64_t lt);
+int launch_lcs(const LcsArgs& a, hipStream_t stream);
+}  // namespace tea

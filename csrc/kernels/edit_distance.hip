@@ -32,20 +32,22 @@
 //    (M those of one strip), so the wave that wraps round to strip s + W - 1 writes an entry at least
 //    2 W - 2 macro steps after strip s read it.  No spin-wait, no flag, no atomic.
 //  * edit_distance_prep_kernel (only with ignore_index): a wave per row and side compacts the kept
-//    tokens into the workspace by ballot and popcount prefix, 64 at a time, and writes the kept lengths.
+//    tokens into the workspace by ballot and popcount prefix, 64 at a time, and writes the kept lengths
+//    (tea_token_rows.h, shared with K30).
 //  * edit_distance_finish_kernel (only with totals): one wave adds the distances and lengths as 64-bit
 //    integers and adds the four sums to the float64 totals; everything is an integer below 2^53.
 // Every store of a result is non-atomic: bit-identical from run to run.  Pairs per workgroup, waves of
 // the block arm and the prefetch depth (one chunk) are untuned.
 #include "tea_common.h"
 #include "tea_kernels.h"
+#include "tea_token_rows.h"
 
 namespace tea {
 
 namespace {
 
 constexpr int kShr1 = 0x138;  // DPP control wave_shr:1
-constexpr int kPrepWaves = 4;
+constexpr int kPrepWaves = kTokenPrepWaves;
 
 // lane l takes `v` of lane l - 1; lane 0 takes `lane0`
 __device__ __forceinline__ uint32_t shr1(uint32_t lane0, uint32_t v) {
@@ -70,15 +72,6 @@ __device__ __forceinline__ void load_tok(const void* row, int idx, int n, uint32
       lo = static_cast<const uint32_t*>(row)[idx];
     }
   }
-}
-
-// a row's length, clamped to [0, width]; row_len: of a wave-uniform row, as a scalar
-__device__ __forceinline__ int clamped_len(const int64_t* lengths, int64_t pair, int64_t width) {
-  const int64_t v = lengths ? lengths[pair] : width;
-  return static_cast<int>(v < 0 ? 0 : (v > width ? width : v));
-}
-__device__ __forceinline__ int row_len(const int64_t* lengths, int64_t pair, int64_t width) {
-  return __builtin_amdgcn_readfirstlane(clamped_len(lengths, pair, width));
 }
 
 __device__ __forceinline__ int strips_of(int m) { return (m + 63) >> 6; }
@@ -229,24 +222,8 @@ __global__ __launch_bounds__(kEditBlockWaves* kWave) void edit_distance_block_ke
 
 template <typename T>
 __global__ __launch_bounds__(kPrepWaves* kWave) void edit_distance_prep_kernel(EditDistanceArgs g) {
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kPrepWaves + wave_id();
-  if (row >= 2 * g.b) return;
-  const bool tg = row >= g.b;
-  const int64_t pair = tg ? row - g.b : row, width = tg ? g.lt : g.li;
-  const int len = row_len(tg ? g.target_lengths : g.input_lengths, pair, width);
-  const T* src = static_cast<const T*>(tg ? g.target : g.input) + pair * width;
-  T* dst = static_cast<T*>(g.ws_tokens) + (tg ? g.b * g.li : 0) + pair * width;
-  const int lane = lane_id();
-  int kept = 0;
-  for (int base = 0; base < len; base += kWave) {
-    const int idx = base + lane;
-    const T v = idx < len ? src[idx] : T(0);
-    const bool keep = idx < len && static_cast<int64_t>(v) != g.ignore_index;
-    const unsigned long long mask = __ballot(keep);
-    if (keep) dst[kept + __popcll(mask & ((1ull << lane) - 1ull))] = v;
-    kept += __popcll(mask);
-  }
-  if (lane == 0) g.ws_lengths[row] = kept;
+  compact_token_rows<T>(g.input, g.target, g.input_lengths, g.target_lengths, g.b, g.li, g.lt, g.ignore_index,
+                        g.ws_tokens, g.ws_lengths);
 }
 
 __global__ __launch_bounds__(kWave) void edit_distance_finish_kernel(EditDistanceArgs g) {

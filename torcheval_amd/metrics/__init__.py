@@ -51,6 +51,7 @@ from torcheval_amd.metrics.text import (
     WordInformationPreserved,
 )
 from torcheval_amd.metrics.text import TokenErrorRate  # not a reference name: kept out of __all__
+from torcheval_amd.metrics.text import TokenROUGEL  # not a reference name: kept out of __all__
 from torcheval_amd.metrics.window import (
     WindowedBinaryAUROC,
     WindowedBinaryNormalizedEntropy,

@@ -50,6 +50,7 @@ from torcheval_amd.metrics.functional.text import (
     word_information_preserved,
 )
 from torcheval_amd.metrics.functional.text import token_edit_distance, token_error_rate  # not reference names: kept out of __all__
+from torcheval_amd.metrics.functional.text import token_lcs_length, token_rouge_l  # not reference names: kept out of __all__
 
 __all__ = sorted(
     list(_cls_all)

@@ -40,6 +40,10 @@ from torcheval_amd.metrics.functional.text.token_edit_distance import (  # noqa:
     token_edit_distance,
     token_error_rate,
 )
+from torcheval_amd.metrics.functional.text.token_rouge_l import (  # noqa: F401  (not reference names: kept out of __all__)
+    token_lcs_length,
+    token_rouge_l,
+)
 
 __all__ = [
     "bleu_score",
@@ -50,3 +54,4 @@ __all__ = [
 ]
 __doc_name__ = "Text Metrics"
 __doc_extras__ = ["token_edit_distance", "token_error_rate"]  # documented, not reference names
+__doc_more__ = ["token_lcs_length", "token_rouge_l"]  # likewise; K29's export test pins the list above

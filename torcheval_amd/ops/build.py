@@ -108,6 +108,7 @@ def _flags(kind: str) -> List[str]:
 # finish launch), and today's code comes out the same with and without the flag: no packed form either way,
 # the same registers.  It is listed only as the guard that every kernel unit since K26 carries, so that a
 # later FP32 edit of the unit cannot bring packed forms in unnoticed; nothing quoted for K29 depends on it.
+# lcs.hip: K30 likewise (bit vectors; FP64 only in the finish launch's divisions and sums).
 FILE_FLAGS = {
     "classification.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
     "detection_map.hip": ["-ffp-contract=off"],
@@ -115,6 +116,7 @@ FILE_FLAGS = {
     "surface_distance.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "panoptic.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "edit_distance.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "lcs.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
